@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X.
 
-    python bench.py                                    # 1 GPU, 200 timed steps
+    python bench.py                                    # 1 GPU, 200 timed steps: the headline line only
+    python bench.py --full                             # the same line with everything else below (configs, CPU baselines, ...)
+    python bench.py --steps 50 --dump-outputs DIR      # also writes what the last timed step computed to DIR/*.npy
     python bench.py --gpus 8 --steps 20 --warmup 5     # starts its own 8 ranks (one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W        # the same ranks, started by a launcher
@@ -17,9 +19,9 @@ N GPUs   each GPU owns one outer-dimension shard of 2^28 elements of the N * 2^2
          process is one of the ranks.  torch.distributed (backend nccl = RCCL) provides the barrier and the
          max-over-ranks of the timings only.
          --mode single: one process, one host thread, N devices through libsmhip's device group.
-         --mode single also runs config 3 over the group ("c5"."c3_sharded": 4096 rows per GPU, the row replicated device to device
-         by smhip_copy_peer, smhip_sharded_elementwise -- the replicated-operand path and a real peer copy).
-         Config 5's exchange step (fused add + sum per shard, then ONE ncclAllReduce of an fp64 scalar over xGMI, issued
+         With --full, --mode single also runs config 3 over the group ("c5"."c3_sharded": 4096 rows per GPU, the row replicated
+         device to device by smhip_copy_peer, smhip_sharded_elementwise -- the replicated-operand path and a real peer copy),
+         and config 5's exchange step (fused add + sum per shard, then ONE ncclAllReduce of an fp64 scalar over xGMI, issued
          by libsmhip itself: smhip_allreduce_sum_async / smhip_sharded_contiguous_sum) is timed after the headline
          region and reported under "c5" (operands: config 5's seeds 6/7 in [0,1)).
 roofline dominant kernel = contiguous_vec_kernel<float, AddOp<float>, 1024, false>; algorithmic bytes 12 B/elem (2 reads +
@@ -29,7 +31,7 @@ roofline dominant kernel = contiguous_vec_kernel<float, AddOp<float>, 1024, fals
          kernel runs on) over the timed region / (steps * launches_per_step); peak = 8000 GB/s (MI355X HBM3E spec).  `traffic` is NOT
          measured by this run: it is the HBM byte count of the last committed rocprofv3 --pmc passes
          (tools/pmc_traffic.sh -> profiles/traffic_latest.json) and `traffic_source` says so; null if that file is absent.
-configs  the N = 1 line also carries BASELINE configs 3, 4 and 5's per-GPU step under "configs": {"c3", "c4", "c5_shard"}, each
+configs  with --full, the N = 1 line also carries BASELINE configs 3, 4 and 5's per-GPU step under "configs": {"c3", "c4", "c5_shard"}, each
          timed in TWO settings and priced against the same 8 TB/s:
            replay  every launch re-reads the same operands (the headline's setting).  For configs 3 and 4 the reads fit the
                    256 MiB Infinity Cache, so `bound` reads "hbm+infinity_cache": the rate is cache-fed.
@@ -43,10 +45,17 @@ configs  the N = 1 line also carries BASELINE configs 3, 4 and 5's per-GPU step 
          (ncclCommCount) -- at N > 1 that is how the line shows the collective saw N ranks -- and the N > 1 line adds
          "per_gpu": [{rank, device, kernel_ms, frac}].  `--configs none` leaves the legs out; `--workload W --setting cold`
          runs one workload's whole timed region in the cold setting (what the rocprofv3 summaries under profiles/ time).
-cpu_baseline  rank 0, N = 1 only, on a bounded sample: `value` = the reference's own operator path as shipped (oracle/_ref,
+cpu_baseline  --full, rank 0, N = 1 only, on a bounded sample: `value` = the reference's own operator path as shipped (oracle/_ref,
          kind "reference") if the prebuilt .so travelled, else the oracle's restatement (kind "port"); `best_effort` =
          the restatement on every core this process may use (cgroup quota / affinity / SMT accounted for), output
          preallocated -- the number that does not flatter the GPU.  Per workload, as BASELINE.md section 3 lists them.
+plain    without --full a run sets up, warms up, times --steps steps and prints the line: value, ms_per_step and the roofline
+         of the timed region; the 20 single launches (roofline.kernel_ms_median_of_20_single_launches / kernel_ms_min),
+         "configs", "c5" and "cpu_baseline" are --full's.
+outputs  --dump-outputs DIR writes, after the timed steps, what the last one computed: DIR/c.npy (add, add_sum; add_sum also
+         DIR/sum.npy, the fp64 sum) or DIR/out.npy (the other workloads), float32 as computed; an output of more than 2^22
+         elements is sampled at a fixed, seeded set of 2^22 random indices (sorted, duplicates dropped).  Ranks add _rank<r>,
+         --mode single with N > 1 adds _gpu<g>.  Inputs are seeded: the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -94,6 +103,11 @@ def parse():
     ap.add_argument("--configs", default="all", choices=["all", "none"],
                     help="all = the N=1 `add` line also times BASELINE configs 3, 4 and 5's shard (replay and cold) and the one-rank RCCL leg")
     ap.add_argument("--rank-timeout", type=float, default=900.0, help="seconds after which self-started ranks are killed")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: 20 single launches, the config legs, config 5's exchange "
+                         "step, the CPU baselines (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (outputs above 2^22 elements: a fixed seeded sample)")
     return ap.parse_args()
 
 
@@ -444,7 +458,7 @@ def build_workload(lib, sma, np, C, wl, args, rank, bound, setting="replay", log
     def sets_for(footprint):
         return 1 if setting == "replay" else max(2, -(-COLD_ROTATION_BYTES // footprint))
 
-    steps, keep = [], []
+    steps, keep, outs = [], [], []  # outs[k]: what a step on operand set k computes, by name
     if wl in ("add", "add_sum"):
         log2n = log2n or 28
         n = 1 << log2n
@@ -458,6 +472,7 @@ def build_workload(lib, sma, np, C, wl, args, rank, bound, setting="replay", log
             b = lib.uniform_f32(n, seeds[1] + 100 * k, lo, 1.0, first=first)
             c = lib.empty((n,), F32)
             keep.append((a, b, c))
+            outs.append({"c": c})
             if wl == "add":
                 steps.append(bound(lib.c.smhip_contiguous, C.c_int(sma.OP_ADD), C.c_int(sma.F32), C.c_void_p(a.ptr), C.c_void_p(b.ptr),
                                    C.c_void_p(c.ptr), C.c_size_t(n)))
@@ -468,7 +483,7 @@ def build_workload(lib, sma, np, C, wl, args, rank, bound, setting="replay", log
         kernel = ("contiguous_vec_kernel<float, AddOp<float>, 1024, false>" if wl == "add"
                   else "reduce_kernel<float, AddOp<float>, kFused> (+ finish_kernel)")
         text = f"1D float32 {'add' if wl == 'add' else 'fused add+sum'}, N=2^{log2n} per GPU, contiguous, HBM-resident"
-        extras = {"log2n": log2n, "n": n, "sum_ptr": sum_ptr}
+        extras = {"log2n": log2n, "n": n, "sum_ptr": sum_ptr, "outputs": outs}
         if wl == "add":
             extras["launches_per_step"] = pieces
         else:  # priced per STEP: its launches are two different kernels
@@ -483,10 +498,11 @@ def build_workload(lib, sma, np, C, wl, args, rank, bound, setting="replay", log
             A = lib.uniform_f32(rows * cols, 3 + 100 * k, -1.0, 1.0)
             out = lib.empty((rows, cols), F32)
             keep.append((A, out))
+            outs.append({"out": out})
             steps.append(bound(lib.c.smhip_elementwise, C.c_int(sma.OP_MUL), C.c_int(sma.F32), C.c_void_p(A.ptr), i64([cols, 1]),
                                C.c_void_p(r.ptr), i64([0, 1]), i64([rows, cols]), C.c_int(2), C.c_void_p(out.ptr)))
         return (steps, rows * cols, 4 * (2 * rows * cols + cols), "flat_tile_kernel<float, MultiplyOp<float>, 3, 2, *>",
-                "2D float32 (4096x4096) * (1x4096) broadcast multiply, HBM-resident", keep, {})
+                "2D float32 (4096x4096) * (1x4096) broadcast multiply, HBM-resident", keep, {"outputs": outs})
     if wl == "chain":
         # (A * row + B) * 0.5f -- what SMArray's operators queue for that expression: ONE kernel, A and B streamed, the row
         # from the caches, the two temporaries of the reference's three operator calls (SMArray.h:217-305) never written
@@ -503,11 +519,12 @@ def build_workload(lib, sma, np, C, wl, args, rank, bound, setting="replay", log
             ptrs = (C.c_void_p * 4)(A.ptr, r.ptr, B.ptr, None)
             strides = i64([cols, 1, 0, 1, cols, 1, 0, 0])
             keep.append((A, B, out, ptrs, strides))
+            outs.append({"out": out})
             steps.append(bound(lib.c.smhip_chain, C.c_int(sma.F32), C.c_int(4), ptrs, strides, half.ctypes.data_as(C.c_void_p), ops, swp,
                                i64([rows, cols]), C.c_int(2), C.c_void_p(out.ptr)))
         return (steps, rows * cols, 4 * (3 * rows * cols + cols), "chain_kernel<float, 2, 1, 0, 1>",
                 "2D float32 (A * row + B) * 0.5 on 4096x4096 as one smhip_chain call (3 operators, 1 launch), HBM-resident", keep,
-                {"operators": 3, "eager_bytes_per_element": 28})
+                {"operators": 3, "eager_bytes_per_element": 28, "outputs": outs})
     if wl == "transpose_add":
         rows = cols = 8192
         for k in range(sets_for(12 * rows * cols)):
@@ -515,10 +532,11 @@ def build_workload(lib, sma, np, C, wl, args, rank, bound, setting="replay", log
             B = lib.uniform_f32(rows * cols, 9 + 100 * k, -1.0, 1.0)
             out = lib.empty((cols, rows), F32)
             keep.append((A, B, out))
+            outs.append({"out": out})
             steps.append(bound(lib.c.smhip_elementwise, C.c_int(sma.OP_ADD), C.c_int(sma.F32), C.c_void_p(A.ptr), i64([1, cols]),
                                C.c_void_p(B.ptr), i64([rows, 1]), i64([cols, rows]), C.c_int(2), C.c_void_p(out.ptr)))
         return (steps, rows * cols, 12 * rows * cols, "tile_kernel<float, AddOp<float>, true, 1, 0>",
-                "2D float32 A.T + B, 8192x8192, A read through a transposed view, HBM-resident", keep, {})
+                "2D float32 A.T + B, 8192x8192, A read through a transposed view, HBM-resident", keep, {"outputs": outs})
     log2n = log2n or 26
     n = 1 << log2n
     exponent = C.c_float(2.5)
@@ -527,10 +545,11 @@ def build_workload(lib, sma, np, C, wl, args, rank, bound, setting="replay", log
         a = lib.uniform_f32(n, 5 + 100 * k, 0.01, 100.0)
         out = lib.empty((n,), F32)
         keep.append((a, out))
+        outs.append({"out": out})
         steps.append(bound(lib.c.smhip_array_scalar, C.c_int(sma.OP_POW), C.c_int(sma.F32), C.c_void_p(a.ptr), C.byref(exponent),
                            C.c_size_t(n), C.c_void_p(out.ptr)))
     return (steps, n, 8 * n, "flat_tile_kernel<float, PowOp<float>, 1, 2, *>",
-            f"1D float32 pow(a, 2.5), N=2^{log2n}, a in (0.01,100), HBM-resident", keep, {"log2n": log2n})
+            f"1D float32 pow(a, 2.5), N=2^{log2n}, a in (0.01,100), HBM-resident", keep, {"log2n": log2n, "outputs": outs})
 
 
 def bound_reads(wl, setting, alg_bytes):
@@ -560,6 +579,50 @@ def time_steps(lib, steps, n_steps, warmup, barrier=None):
     return ms, wall
 
 
+DUMP_SAMPLE = 1 << 22  # elements --dump-outputs keeps of a larger output (16 MiB of float32)
+DUMP_CHUNK = 64 << 20  # bytes per download while sampling
+
+
+def sample_index(np, n):
+    """The elements --dump-outputs keeps of an n-element output: None (all of them) up to DUMP_SAMPLE, else a fixed, seeded
+    set of indices, sorted."""
+    if n <= DUMP_SAMPLE:
+        return None
+    return np.unique(np.random.default_rng(20261016).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+
+
+def download_sample(lib, np, arr):
+    """A dense device array on the host, or its sample_index elements, downloaded DUMP_CHUNK bytes at a time so that the host
+    never holds the whole output."""
+    idx = sample_index(np, arr.size)
+    if idx is None:
+        return arr.numpy().reshape(-1)
+    n = arr.size
+    out = np.empty(idx.size, dtype=arr.dtype)
+    chunk = DUMP_CHUNK // arr.dtype.itemsize
+    buf = np.empty(chunk, dtype=arr.dtype)
+    base, pos = arr.ptr, 0
+    for lo in range(0, n, chunk):
+        hi = min(lo + chunk, n)
+        end = int(np.searchsorted(idx, hi))
+        if end > pos:
+            part = buf[: hi - lo]
+            lib.download(part, base + lo * arr.dtype.itemsize)
+            out[pos:end] = part[idx[pos:end] - lo]
+            pos = end
+    return out
+
+
+def dump_outputs(lib, np, outdir, outputs, suffix=""):
+    """--dump-outputs: {name: dense device array, or host array} -> outdir/<name><suffix>.npy, float32 / float64 as computed."""
+    os.makedirs(outdir, exist_ok=True)
+    lib.synchronize()
+    for name, arr in outputs.items():
+        host = arr if isinstance(arr, np.ndarray) else download_sample(lib, np, arr)
+        assert host.dtype in (np.float32, np.float64), (name, host.dtype)
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), host)
+
+
 def config_legs(lib, sma, np, C, args, bound):
     """BASELINE configs 3, 4 and 5's per-GPU step, each replayed and cold, on the current device (rank 0, N = 1)."""
     legs = {}
@@ -587,7 +650,7 @@ def config_legs(lib, sma, np, C, args, bound):
                 leg[setting]["rotating_bytes"] = len(steps) * alg_bytes
             if "sum_ptr" in info:
                 lib.free(info["sum_ptr"])
-            del steps, keep
+            del steps, keep, info
             lib.synchronize()
             lib.pool_trim()
         legs[key] = leg
@@ -666,10 +729,12 @@ def emit(args, wl, world, mode, value, ms_per_step, units, alg_bytes, kern_ms, s
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                      "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": kern_ms,
                      "launches_per_step": launches_per_step, "algorithmic_bytes_per_step": alg_bytes_step, "step_kernel_ms": step_kern_ms,
-                     "kernel_ms_median_of_20_single_launches": singles[len(singles) // 2], "kernel_ms_min": singles[0],
                      "per_gpu": "slowest GPU's average launch" if world > 1 else "the GPU's average launch",
                      "peak_source": "MI355X HBM3E 8.0 TB/s spec (MI355X_MICROARCH.md); the guide's measured float4 copy is 6.29 TB/s"},
     }
+    if singles:  # --full
+        line["roofline"]["kernel_ms_median_of_20_single_launches"] = singles[len(singles) // 2]
+        line["roofline"]["kernel_ms_min"] = singles[0]
     if step_launches:
         line["roofline"]["step_launches"] = step_launches
     if c5:
@@ -727,7 +792,8 @@ def run_rank(args):
     lib = sma.load()  # raises if the HIP library is missing: no CPU fallback
     lib.set_device(local_rank)
 
-    use_lib_comm = dist_on and args.dist_backend == "nccl"
+    need_c5 = args.full and args.workload == "add" and dist_on  # config 5's exchange step: --full only
+    use_lib_comm = need_c5 and args.dist_backend == "nccl"
     comm_error = None
     if use_lib_comm:
         # libsmhip's own communicator for config 5's all-reduce: the unique id travels over torch.distributed.  A failure
@@ -773,6 +839,7 @@ def run_rank(args):
     wl = args.workload
     steps, units, alg_bytes, kernel, workload, keep, info = build_workload(lib, sma, np, C, wl, args, rank, bound, args.setting)
     K = len(steps)
+    outputs = info.pop("outputs")
 
     # Clock ramp: the chip needs tens of milliseconds of continuous work to leave its idle clocks (a VALU-heavy launch
     # measures 115 us cold and 94 us ramped), and W short steps may not last that long.
@@ -785,6 +852,12 @@ def run_rank(args):
         lib.synchronize()
     kern_ms, wall = time_steps(lib, steps, args.steps, args.warmup, barrier)  # barrier + synchronise on both sides of exactly K steps
     my_kern_ms = kern_ms
+    if args.dump_outputs:
+        last = dict(outputs[(args.steps - 1) % K])  # the operand set the last timed step used
+        if wl == "add_sum":
+            last["sum"] = np.array([lib.read_f64(info["sum_ptr"])], dtype=np.float64)
+        dump_outputs(lib, np, args.dump_outputs, last, f"_rank{rank}" if world > 1 else "")
+    del outputs
 
     coll_dev = "cuda" if (dist is not None and args.dist_backend == "nccl") else "cpu"
     per_gpu = None
@@ -799,17 +872,18 @@ def run_rank(args):
         per_gpu = [{"rank": r, "device": int(mine[r, 1]), "kernel_ms": float(mine[r, 0]) / lps,
                     "frac": alg_bytes / (float(mine[r, 0]) * 1e-3) / 1e9 / HBM_PEAK_GBS} for r in range(world)]
 
-    # per-launch distribution (SURVEY 8d asks for median and min): 20 launches timed one by one, after the
+    # per-launch distribution (SURVEY 8d asks for median and min, --full): 20 launches timed one by one, after the
     # contract's timed region so the extra event records do not touch it
     singles = []
-    e0, e1 = lib.event(), lib.event()
-    for i in range(20):
-        lib.record(e0)
-        steps[i % K]()
-        lib.record(e1)
-        lib.event_sync(e1)
-        singles.append(lib.elapsed_ms(e0, e1))
-    singles.sort()
+    if args.full:
+        e0, e1 = lib.event(), lib.event()
+        for i in range(20):
+            lib.record(e0)
+            steps[i % K]()
+            lib.record(e1)
+            lib.event_sync(e1)
+            singles.append(lib.elapsed_ms(e0, e1))
+        singles.sort()
 
     ms_per_step = wall / args.steps * 1e3
     value = world * units / (wall / args.steps) / 1e9
@@ -817,7 +891,7 @@ def run_rank(args):
     # config 5's exchange step: fused add+sum per shard, then ONE all-reduce of the fp64 scalar
     c5 = None
     rccl = None
-    if wl == "add" and dist_on:
+    if need_c5:
         n, log2n = info["n"], info["log2n"]
         del keep, steps  # the headline operands go back to the pool; config 5 has its own (seeds 6/7 in [0,1))
         a5 = lib.uniform_f32(n, 6, 0.0, 1.0, first=rank * n)
@@ -868,7 +942,7 @@ def run_rank(args):
             extra["per_gpu"] = per_gpu
         if rccl is not None:
             extra["rccl"] = rccl
-        if world == 1 and wl == "add" and args.configs == "all" and not dist_on and args.setting == "replay":
+        if args.full and world == 1 and wl == "add" and args.configs == "all" and not dist_on and args.setting == "replay":
             # the other BASELINE configs, replayed and cold, and config 5's exchange step with one rank through libsmhip's own group
             steps = keep = None
             lib.pool_trim()
@@ -879,7 +953,7 @@ def run_rank(args):
                 for key, cwl in (("c3", "bcast_mul"), ("c4", "pow"), ("c5_shard", "add_sum"), ("chain", "chain")):
                     legs[key]["cpu_baseline"] = cpu_baseline(cwl, args.cpu_log2n)
             extra["configs"] = legs
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(wl, args.cpu_log2n)
             if cb is not None:
                 extra["cpu_baseline"] = cb
@@ -945,6 +1019,8 @@ def run_single(args):
     pt = lambda arrs: (C.c_void_p * G)(*[x.ptr for x in arrs])
     ns = (C.c_size_t * G)(*([n] * G))
     pa, pb, pc = pt(aa), pt(bb), pt(cc)
+    headline = [aa, bb, cc]  # the only references left: --full's legs empty it before they allocate their own operands
+    del aa, bb
 
     def step():
         rc = lib.c.smhip_sharded_contiguous(C.c_int(sma.OP_ADD), C.c_int(sma.F32), pa, pb, pc, ns)
@@ -983,7 +1059,38 @@ def run_single(args):
     wall = time.perf_counter() - t0
     each_ms = [lib.elapsed_ms(e0, e1) / args.steps for e0, e1 in ev]
     kern_ms = max(each_ms)
+    if args.dump_outputs:
+        for g in range(G):
+            lib.set_device(g)
+            dump_outputs(lib, np, args.dump_outputs, {"c": cc[g]}, f"_gpu{g}" if G > 1 else "")
+    lib.set_device(0)
+    info = [lib.group_info(g) for g in range(G)]
+    extra = {"rccl": {"nranks": info[0][0], "version": lib.rccl_version(), "communicators": [{"rank": r, "device": d, "nranks": nr} for nr, r, d in info],
+                      "source": "ncclCommCount / ncclCommUserRank / ncclCommCuDevice / ncclGetVersion through libsmhip (smhip_group_info, smhip_rccl_version)"},
+             "per_gpu": [{"rank": g, "device": g, "kernel_ms": each_ms[g] / lib.launch_pieces(4 * n),
+                          "frac": 12 * n / (each_ms[g] * 1e-3) / 1e9 / HBM_PEAK_GBS} for g in range(G)]}
+    singles, c5 = [], None
+    if args.full:
+        del cc
+        singles, c5 = single_mode_full(lib, sma, np, C, args, step, ev, headline, on_each, pt, ns)
+        if G == 1 and not args.no_cpu_baseline:
+            cb = cpu_baseline("add", args.cpu_log2n)
+            if cb is not None:
+                extra["cpu_baseline"] = cb
+    emit(args, "add", G, "single", G * n / (wall / args.steps) / 1e9, wall / args.steps * 1e3, n, 12 * n, kern_ms, singles,
+         "contiguous_vec_kernel<float, AddOp<float>, 1024, false>",
+         f"1D float32 add, N=2^{log2n} per GPU, contiguous, HBM-resident", c5, extra, "replay", lib.launch_pieces(4 * n))
+    lib.set_devices(0)
+    return 0
 
+
+def single_mode_full(lib, sma, np, C, args, step, ev, headline, on_each, pt, ns):
+    """--mode single --full: 20 single launches of the headline step, config 5's exchange step and config 3 over the group.
+    Empties `headline` (the headline's operands) after the single launches.  -> (sorted single-launch ms, the "c5" object)"""
+    G = args.gpus
+    log2n = args.log2n or 28
+    n = 1 << log2n
+    F32 = np.float32
     lib.set_device(0)
     singles = []
     for _ in range(20):
@@ -995,7 +1102,7 @@ def run_single(args):
     singles.sort()
 
     # config 5: fused add+sum on every device + ONE ncclAllReduce inside ncclGroupStart/End, scalar back to the host
-    del aa, bb, cc
+    headline.clear()
     a5, b5, c5o = on_each(6, 7, 0.0)
     pa, pb, pc = pt(a5), pt(b5), pt(c5o)
     total = C.c_double(0)
@@ -1071,21 +1178,7 @@ def run_single(args):
                         "entry": "smhip_sharded_elementwise (no collective)", "ms_per_step": t3 * 1e3, "value": G * rows * cols / t3 / 1e9, "unit": "Gelem/s",
                         "per_gpu_frac_of_8TBps": c3_bytes / t3 / 1e9 / HBM_PEAK_GBS, "peer_copies": G - 1, "blocks_match_single_device_result": all(block_ok),
                         "note": "host clock over 100 steps of G launches each (replayed operands: cache-fed, like configs.c3.replay)"}
-
-    info = [lib.group_info(g) for g in range(G)]
-    extra = {"rccl": {"nranks": info[0][0], "version": lib.rccl_version(), "communicators": [{"rank": r, "device": d, "nranks": nr} for nr, r, d in info],
-                      "source": "ncclCommCount / ncclCommUserRank / ncclCommCuDevice / ncclGetVersion through libsmhip (smhip_group_info, smhip_rccl_version)"},
-             "per_gpu": [{"rank": g, "device": g, "kernel_ms": each_ms[g] / lib.launch_pieces(4 * n),
-                          "frac": 12 * n / (each_ms[g] * 1e-3) / 1e9 / HBM_PEAK_GBS} for g in range(G)]}
-    if G == 1 and not args.no_cpu_baseline:
-        cb = cpu_baseline("add", args.cpu_log2n)
-        if cb is not None:
-            extra["cpu_baseline"] = cb
-    emit(args, "add", G, "single", G * n / (wall / args.steps) / 1e9, wall / args.steps * 1e3, n, 12 * n, kern_ms, singles,
-         "contiguous_vec_kernel<float, AddOp<float>, 1024, false>",
-         f"1D float32 add, N=2^{log2n} per GPU, contiguous, HBM-resident", c5, extra, "replay", lib.launch_pieces(4 * n))
-    lib.set_devices(0)
-    return 0
+    return singles, c5
 
 
 def main():

@@ -35,17 +35,6 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def reference():
-    """The compiled reference (only where oracle/_ref/libsmref.so exists)."""
-    from oracle import oracle as orc
-    if not orc.Reference.available() and os.path.isdir("/root/reference/include"):
-        orc.build(ref=True)  # the reference compiled from where it lies; outputs only under oracle/_ref/
-    if not orc.Reference.available():
-        pytest.skip("oracle/_ref/libsmref.so not built (needs /root/reference)")
-    return orc.Reference()
-
-
-@pytest.fixture(scope="session")
 def smhip():
     """The product C-ABI (libsmhip.so) on a real GPU; fails loudly if it is missing."""
     import simplemath_amd as sma

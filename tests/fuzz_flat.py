@@ -1,7 +1,7 @@
 """Randomised 1-D forms against the oracle: contiguous, array-scalar, fused and reduction entry points on random lengths
 (every tail) and random element offsets (every misalignment), all element types.   usage: fuzz_flat.py [cases] [seed]"""
-import sys
-sys.path.insert(0, "/root/repo")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import math
 import numpy as np
 import simplemath_amd as sma

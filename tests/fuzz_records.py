@@ -2,8 +2,8 @@
 rows) through smhip_elementwise and smhip_copy_strided: the record kernel, the tile kernel's short patch and whatever the
 planner falls back to, against numpy (one correctly rounded operation per element).
 usage: python tests/fuzz_records.py [cases] [seed]      -- prints the first mismatch and exits 1, else "ok"."""
-import sys
-sys.path.insert(0, "/root/repo")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import simplemath_amd as sma
 from tests.golden import gen

@@ -3,8 +3,8 @@ smhip_elementwise, and random strided assignments through smhip_copy_strided (nu
 
 usage: python tests/fuzz_views.py [cases] [seed]      -- prints the first mismatch and exits 1, else "ok".
 """
-import sys
-sys.path.insert(0, "/root/repo")
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import simplemath_amd as sma
 from oracle import oracle as orc

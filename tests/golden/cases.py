@@ -303,3 +303,50 @@ def digest(*arrays) -> str:
     for a in arrays:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()
+
+
+# ------------------------------------------------- the reference on random inputs (test_oracle.py section 3)
+# The reference's answers for these inputs are recorded once (make_golden.py live_reference -> live_reference.npz), so the
+# oracle is checked against them wherever the suite runs, with or without the reference tree.
+def live_random_cases():
+    """200 random broadcast pairs of rank 2-6, extents 1-5: (trial, dtype name, op, a, b)."""
+    rng = np.random.default_rng(1234)
+    out = []
+    for trial in range(200):
+        nd = int(rng.integers(2, 7))
+        shape = [int(rng.integers(1, 6)) for _ in range(nd)]
+        ash = [d if rng.random() < 0.7 else 1 for d in shape]
+        bsh = [d if rng.random() < 0.7 else 1 for d in shape][int(rng.integers(0, nd - 1)):]
+        dtn = ["f32", "f64", "i32"][trial % 3]
+        op = BINOPS[trial % 4]
+        a = gen.gen(DT[dtn], int(np.prod(ash)), 5000 + trial, "mixed").reshape(ash)
+        kb = "nonzero" if (dtn == "i32" and op == "div") else "mixed"
+        b = gen.gen(DT[dtn], int(np.prod(bsh)), 6000 + trial, kb).reshape(bsh)
+        out.append((trial, dtn, op, a, b))
+    return out
+
+
+def live_smarray_inputs():
+    """SMArray's operator glue: a (13, 17) and a (17, 13) f32 array; a (2, 5, 4, 3) array and its (1, 5, 1, 3) partner."""
+    a = gen.gen(np.float32, 13 * 17, 1, "uniform").reshape(13, 17)
+    b = gen.gen(np.float32, 13 * 17, 2, "uniform").reshape(17, 13)
+    big = gen.gen(np.float32, 2 * 5 * 4 * 3, 3, "uniform").reshape(2, 5, 4, 3)
+    small = gen.gen(np.float32, 15, 4, "uniform").reshape(1, 5, 1, 3)
+    return a, b, big, small
+
+
+def live_dot_cases():
+    """Every n from 1 to 70: (n, complex128 a, b, {integer dtype name: (x, y)})."""
+    rng = np.random.default_rng(99)
+    out = []
+    for n in range(1, 71):
+        a = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+        b = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+        ints = {}
+        for dt in GDOT_DTYPES:
+            info = np.iinfo(dt)
+            x = rng.integers(info.min, info.max, size=n, dtype=dt, endpoint=True)
+            y = rng.integers(info.min, info.max, size=n, dtype=dt, endpoint=True)
+            ints[dt] = (x, y)
+        out.append((n, a, b, ints))
+    return out

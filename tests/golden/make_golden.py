@@ -17,6 +17,7 @@ through oracle/_ref/libsmref.so (oracle/ref_shim.cpp).  Outputs:
     tests/golden/dot_extra.npz    dot_product<std::complex<double>> and the generic dot_product<T> (product.h:168-224, :8-20)
     tests/golden/bench_sizes.npz  the contiguous / scalar / int-pow loops at the sizes the reference benchmarks and tests at
                                   (benchmark/add.cpp:21-29: N = 1 000 000; calculate.h:152's gate: 100 003; tests/pow.cpp:46-61: 2 000 000)
+    tests/golden/live_reference.npz  the answers test_oracle.py's random cases check the oracle against (cases.live_*)
     tests/golden/powf.npz         PowOp<float>::apply = glibc powf (pow.h:8-10) AND the
                                   correctly-rounded value computed in fp64 (the parity target;
                                   the reference itself pins no float pow -- SURVEY 8c)
@@ -88,10 +89,47 @@ def make_bench_sizes(ref):
     print("bench_sizes:", len(st) // 4, "cases")
 
 
+def make_live_reference(ref):
+    """The reference's answers for test_oracle.py's random cases (cases.live_*): broadcast strides and element-wise outputs of
+    200 random pairs, SMArray's operator glue, the complex and generic dots for every n from 1 to 70."""
+    st = {}
+    ins = []
+    for trial, dtn, op, a, b in cases.live_random_cases():
+        ins += [a, b]
+        shape, sa, sb, total = ref.broadcast(a.shape, orc.elem_strides(a), b.shape, orc.elem_strides(b))
+        st[f"rand{trial}/bcast"] = np.array([len(shape)] + shape + sa + sb + [total], dtype=np.int64)
+        if len(shape) > 1:
+            st[f"rand{trial}/out"] = ref.elementwise(orc.OPS[op], a.reshape(-1), sa, b.reshape(-1), sb, shape)
+    st["rand/in_sha"] = _sha_arr(np.concatenate([x.reshape(-1).view(np.uint8) for x in ins]))
+
+    a, b, big, small = cases.live_smarray_inputs()
+    st["smarray/a_minus_bT"] = ref.smarray_binary(orc.SUB, a, b, bt=True)
+    try:
+        ref.smarray_binary(orc.ADD, a, b)
+        st["smarray/incompatible_refused"] = np.array([0], dtype=np.uint8)
+    except RuntimeError:
+        st["smarray/incompatible_refused"] = np.array([1], dtype=np.uint8)
+    st["smarray/view4d"] = ref.view_broadcast4(orc.MUL, big, small)
+    st["smarray/in_sha"] = _sha_arr(np.concatenate([x.reshape(-1).view(np.uint8) for x in (a, b, big, small)]))
+
+    dots = cases.live_dot_cases()
+    st["dot/c64"] = np.array([ref.dot_c64(a, b) for _, a, b, _ in dots], dtype=np.complex128)
+    st["dot/c32"] = np.array([ref.dot_c32(a.astype(np.complex64), b.astype(np.complex64)) for _, a, b, _ in dots], dtype=np.complex64)
+    for dt in cases.GDOT_DTYPES:
+        st[f"dot/{dt}"] = np.array([ref.dot_int(*ints[dt]) for _, _, _, ints in dots], dtype=dt)
+    st["dot/in_sha"] = _sha_arr(np.concatenate([x.view(np.uint8) for _, a, b, ints in dots
+                                                for x in [a, b] + [v for xy in ints.values() for v in xy]]))
+    np.savez_compressed(os.path.join(HERE, "live_reference.npz"), **st)
+    print("live_reference:", len(st), "arrays")
+
+
 def main():
     ref = orc.Reference()
     if sys.argv[1:] == ["dot_extra"]:  # only the file added in round 3 (the others stay byte-identical in git)
         make_dot_extra(ref)
+        return
+    if sys.argv[1:] == ["live_reference"]:  # only the file that lets test_oracle.py check without the reference tree
+        make_live_reference(ref)
         return
     if sys.argv[1:] == ["bench_sizes"]:  # only the file added in round 4
         make_bench_sizes(ref)
@@ -149,6 +187,7 @@ def main():
 
     make_dot_extra(ref)
     make_bench_sizes(ref)
+    make_live_reference(ref)
 
     st = {}
     for c in cases.powf_cases():

@@ -124,7 +124,7 @@ def test_two_ranks_rehearsal_on_one_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--log2n", "24", "--dist-backend", "gloo"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--log2n", "24", "--dist-backend", "gloo", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -144,7 +144,7 @@ def test_single_process_mode_through_rccl():
     """`--mode single`: one process, the device group (here one device), the sharded entry points, and config 5's
     ncclAllReduce issued by libsmhip inside ncclGroupStart/End."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--mode", "single", "--steps", "5", "--warmup", "2",
-                        "--log2n", "24", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--log2n", "24", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["n_gpus"] == 1 and "one process" in d["config"]["processes"] and 0 < d["roofline"]["frac"] < 1
@@ -160,7 +160,7 @@ def test_rank_mode_through_rccl_with_one_rank():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", SMHIP_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                        "--log2n", "24", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--log2n", "24", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]   # ONE JSON line on stdout (RCCL's banner goes to stderr)
@@ -169,3 +169,69 @@ def test_rank_mode_through_rccl_with_one_rank():
     c5 = d["c5"]
     assert "libsmhip -> ncclAllReduce" in c5["allreduce"], c5
     assert abs(c5["global_sum"] - n) < 6 * (n / 6.0) ** 0.5 and c5["value"] > 0
+
+
+def test_dump_sample_is_fixed_and_read_in_chunks(monkeypatch):
+    """--dump-outputs keeps a small output whole and a large one at a fixed, seeded set of sorted indices, read piece by piece."""
+    import numpy as np
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 1000)
+    monkeypatch.setattr(b, "DUMP_CHUNK", 4096)
+
+    class Arr:  # a dense device array whose memory is the host array `h`
+        def __init__(self, h):
+            self.h, self.size, self.dtype, self.ptr = h, h.size, h.dtype, 0
+
+        def numpy(self):
+            return self.h.copy()
+
+    class Lib:
+        def __init__(self):
+            self.reads = 0
+
+        def download(self, out, ptr):
+            i = ptr // h.itemsize
+            assert out.nbytes <= 4096 and i + out.size <= h.size
+            out[:] = h[i:i + out.size]
+            self.reads += 1
+
+    h = np.random.default_rng(5).standard_normal(100_003).astype(np.float32)
+    lib = Lib()
+    got = b.download_sample(lib, np, Arr(h))
+    idx = b.sample_index(np, h.size)
+    assert idx.dtype == np.int64 and np.all(np.diff(idx) > 0) and 900 < idx.size <= 1000
+    assert np.array_equal(idx, b.sample_index(np, h.size))  # the same indices on every run
+    assert got.dtype == np.float32 and np.array_equal(got, h[idx]) and 1 < lib.reads <= -(-h.nbytes // 4096)
+    small = h[:1000]
+    assert b.sample_index(np, small.size) is None and np.array_equal(b.download_sample(Lib(), np, Arr(small)), small)
+
+
+def test_full_and_dump_outputs_are_options():
+    r, _ = _run_bench(["--help"], timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path, oracle):
+    """A plain run: the timed steps and the line, nothing of --full's; --dump-outputs writes the last step's c = a + b (the
+    whole output at 2^20 elements, the seeded sample at 2^23), bit for bit the oracle's sum of the same seeded inputs."""
+    import numpy as np
+    from oracle import oracle as orc
+    b = _bench()
+    for log2n in (20, 23):
+        out = tmp_path / f"n{log2n}"
+        r, _ = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--log2n", str(log2n), "--dump-outputs", str(out)], timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["metric"] == b.BASELINE_METRIC and d["unit"] == "Gelem/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] - (1 << log2n) / (d["ms_per_step"] * 1e-3) * 1e-9) < 1e-6 * d["value"]
+        assert not {"configs", "cpu_baseline", "c5"} & set(d) and "kernel_ms_median_of_20_single_launches" not in d["roofline"]
+        n = 1 << log2n
+        want = oracle.contiguous(orc.ADD, oracle.uniform_f32(n, 1, -1.0, 1.0), oracle.uniform_f32(n, 2, -1.0, 1.0))
+        idx = b.sample_index(np, n)
+        got = np.load(out / "c.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, want if idx is None else want[idx])
+        assert sorted(os.listdir(out)) == ["c.npy"]

@@ -6,7 +6,7 @@ f32 / f64 / i32, + and *, a user-defined Op (hipRTC compiles the same body), bit
 per element).                    python tests/tile_probe.py [big]      -- prints "tile_probe ok <cases>".
 """
 import os, sys
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import simplemath_amd as sma
 from tests.golden import gen

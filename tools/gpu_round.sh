@@ -10,10 +10,10 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -q -m gpu > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $out/pytest_gpu.log
 tail -3 $out/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log
-timeout -k 10 300 python bench.py > $out/bench_add.json 2> $out/bench_add.err; echo "bench rc=$?"; cut -c1-600 $out/bench_add.json
-timeout -k 10 300 python bench.py --gpus 1 --mode single --no-cpu-baseline > $out/bench_add_single.json 2> $out/bench_add_single.err; echo "bench single rc=$?"
+timeout -k 10 300 python bench.py --full > $out/bench_add.json 2> $out/bench_add.err; echo "bench rc=$?"; cut -c1-600 $out/bench_add.json
+timeout -k 10 300 python bench.py --gpus 1 --mode single --no-cpu-baseline --full > $out/bench_add_single.json 2> $out/bench_add_single.err; echo "bench single rc=$?"
 for wl in bcast_mul pow add_sum transpose_add; do
-  timeout -k 10 200 python bench.py --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err; echo "bench $wl rc=$?"
+  timeout -k 10 200 python bench.py --workload $wl --full > $out/bench_$wl.json 2> $out/bench_$wl.err; echo "bench $wl rc=$?"
 done
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$out/prof_add -- python3 $GRAFT_REPO_ROOT/bench.py --steps 200 --warmup 20 --no-cpu-baseline > $GRAFT_REPO_ROOT/$out/prof_add.log 2>&1; echo "rocprof add rc=$?"

@@ -15,12 +15,12 @@ if [ "$part" = a ]; then
   timeout -k 10 900 python -m pytest tests -q -m gpu > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $out/pytest_gpu.log
   tail -3 $out/pytest_gpu.log
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log
-  timeout -k 10 300 python bench.py > $out/bench_add.json 2> $out/bench_add.err; echo "bench rc=$?"; cut -c1-400 $out/bench_add.json
-  timeout -k 10 300 python bench.py --gpus 1 --mode single --no-cpu-baseline > $out/bench_add_single.json 2> $out/bench_add_single.err; echo "bench single rc=$?"
+  timeout -k 10 300 python bench.py --full > $out/bench_add.json 2> $out/bench_add.err; echo "bench rc=$?"; cut -c1-400 $out/bench_add.json
+  timeout -k 10 300 python bench.py --gpus 1 --mode single --no-cpu-baseline --full > $out/bench_add_single.json 2> $out/bench_add_single.err; echo "bench single rc=$?"
   # the driver's N > 1 launch line with one rank: torch.distributed over RCCL + libsmhip's communicator
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --configs none > $out/bench_torchrun1.json 2> $out/bench_torchrun1.err; echo "bench torchrun rc=$?"
   for wl in bcast_mul pow add_sum transpose_add; do
-    timeout -k 10 200 python bench.py --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err; echo "bench $wl rc=$?"
+    timeout -k 10 200 python bench.py --workload $wl --full > $out/bench_$wl.json 2> $out/bench_$wl.err; echo "bench $wl rc=$?"
   done
   for wl in bcast_mul pow add_sum; do
     timeout -k 10 200 python bench.py --workload $wl --setting cold --no-cpu-baseline > $out/bench_${wl}_cold.json 2> $out/bench_${wl}_cold.err; echo "bench $wl cold rc=$?"
