@@ -89,6 +89,7 @@ struct FusionStats {
     unsigned long long single_ops = 0;    // deferred operators that ended up alone and ran as the plain operator
     unsigned long long direct_assignments = 0;  // `x = <expression>` evaluated straight into x (no temporary, no copy)
     unsigned long long summed_chains = 0;       // `(<expression>).sum()` taken in the chain's own pass, the value never written
+    unsigned long long reductions = 0;          // axis reductions (smhip_reduce_axes: sum / mean / max / min along axes)
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -702,6 +703,27 @@ public:
         return s;
     }
 
+    // Reductions ALONG AXES (np.sum / np.mean / np.max / np.min with `axis`), resident on the device like every result:
+    //   sum   f32: fp64 accumulation, rounded once; f64: fp64; integers: wrapping in T (np.sum(x, axis, dtype=T))
+    //   mean  fp64 sum / count, rounded once (floating-point T only: a static_assert)
+    //   max / min  exact, NaN propagates
+    // `axis` counts from the end when negative; a list names several axes.  A bad or repeated axis throws std::runtime_error.
+    // keepdims = true keeps each reduced axis as an extent of 1 (the result then broadcasts straight back into an operator
+    // chain: `(n - n.mean(0, true)) / s`); reducing every axis without keepdims gives shape {1} -- SMArray has no 0-d form.
+    // A pending operator chain as the operand is evaluated first; the reduction is ONE smhip_reduce_axes call (counted in
+    // sm::fusion_stats().reductions).  The whole-array `double sum()` above is unchanged.
+    SMArray sum(int axis, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_SUM, {axis}, keepdims); }
+    SMArray sum(std::initializer_list<int> axes, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_SUM, axes, keepdims); }
+    SMArray mean(int axis, bool keepdims = false) const { return mean(std::initializer_list<int>{axis}, keepdims); }
+    SMArray mean(std::initializer_list<int> axes, bool keepdims = false) const {
+        static_assert(std::is_floating_point_v<T>, "mean(): the mean of an integer type is not offered (sum() and divide)");
+        return reduce_along(SMHIP_REDUCE_MEAN, axes, keepdims);
+    }
+    SMArray max(int axis, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_MAX, {axis}, keepdims); }
+    SMArray max(std::initializer_list<int> axes, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_MAX, axes, keepdims); }
+    SMArray min(int axis, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_MIN, {axis}, keepdims); }
+    SMArray min(std::initializer_list<int> axes, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_MIN, axes, keepdims); }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -885,6 +907,32 @@ private:
         if (st->inline_uses != 0) return 0;
         const std::size_t bytes = (st->count - data.offset()) * sizeof(T);
         return bytes <= SMHIP_INLINE_MAX_BYTES ? bytes : 0;
+    }
+
+    SMArray reduce_along(int kind, std::initializer_list<int> axes, bool keepdims) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "axis reductions: f32, f64, i32 and i64");
+        const int nd = static_cast<int>(_shape.size());
+        std::uint32_t mask = 0;
+        for (int ax : axes) {
+            const int a = ax < 0 ? ax + nd : ax;
+            if (a < 0 || a >= nd) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(ax) + " out of range for rank " + std::to_string(nd));
+            if (mask >> a & 1u) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(ax) + " repeated");
+            mask |= 1u << a;
+        }
+        if (!mask) throw std::runtime_error("simpleMath/MI355X: no axis to reduce");
+        std::vector<std::size_t> shape;
+        for (int d = 0; d < nd; ++d) {
+            if (!(mask >> d & 1u)) shape.push_back(_shape[d]);
+            else if (keepdims) shape.push_back(1);
+        }
+        if (shape.empty()) shape.push_back(1);
+        hip::DeviceGuard on(device());
+        const T *in = device_data();  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(std::move(shape));
+        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
+        hip::check(smhip_reduce_axes(kind, hip::dtype_of<T>::id, in, sh.data(), st.data(), nd, mask, out.device_data_mut()));
+        ++detail::tls_fusion_stats.reductions;
+        return out;
     }
 
     // Device pointer to a dense version of this array (itself when already dense).

@@ -183,6 +183,26 @@ double sum(SMArray<T> &&arr) {  // sm::sum(sm::pow(a - b, 2.0f)): the expression
     return std::move(arr).sum();
 }
 
+// Reductions along axes (np.sum / np.mean / np.max / np.min with `axis`): SMArray<T> resident on the device.  `axis` is one
+// int (negative counts from the end) or a list {0, 2}; keepdims keeps reduced axes as extents of 1; reducing every axis
+// without keepdims gives shape {1}.  Semantics as SMArray::sum(axis) (SMArray.h) and smhip_reduce_axes (smhip.h).
+template <typename T>
+SMArray<T> sum(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.sum(axis, keepdims); }
+template <typename T>
+SMArray<T> sum(const SMArray<T> &arr, std::initializer_list<int> axes, bool keepdims = false) { return arr.sum(axes, keepdims); }
+template <typename T>
+SMArray<T> mean(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.mean(axis, keepdims); }
+template <typename T>
+SMArray<T> mean(const SMArray<T> &arr, std::initializer_list<int> axes, bool keepdims = false) { return arr.mean(axes, keepdims); }
+template <typename T>
+SMArray<T> max(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.max(axis, keepdims); }
+template <typename T>
+SMArray<T> max(const SMArray<T> &arr, std::initializer_list<int> axes, bool keepdims = false) { return arr.max(axes, keepdims); }
+template <typename T>
+SMArray<T> min(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.min(axis, keepdims); }
+template <typename T>
+SMArray<T> min(const SMArray<T> &arr, std::initializer_list<int> axes, bool keepdims = false) { return arr.min(axes, keepdims); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

@@ -247,6 +247,42 @@ int smhip_chain_sum_async(int dtype, int n_operands, const void *const *operands
 int smhip_chain_sum(int dtype, int n_operands, const void *const *operands, const int64_t *strides, const void *scalars_host, const int *ops,
                     const int *swapped, const int64_t *shape, int ndim, double *sum_host);
 
+/* ------------------------------------------------------- axis reductions */
+/* np.sum / np.mean / np.max / np.min over chosen axes (the reference reduces only whole arrays: product.h).  The contract:
+ *   kind   f32                                   f64                i32 / i64
+ *   SUM    fp64 accumulation, rounded once       fp64               wrapping in the type's width (= np.sum(x, axis, dtype=T),
+ *                                                                   bit-exact in any order)
+ *   MEAN   fp64 sum / count, rounded once to T   the same           SMHIP_ERR_UNSUPPORTED
+ *   MAX    exact                                 exact              exact
+ *   MIN    exact                                 exact              exact
+ * NaN propagates through MAX and MIN (as np.max); which zero a +-0 tie returns is not specified.  The sum over an empty
+ * extent is 0; MEAN, MAX or MIN over an empty extent is SMHIP_ERR_INVALID.  Deterministic: the bits depend only on the dtype,
+ * the kind, the shape and the layout after merging axes -- a fixed partition of the work, partials combined in a fixed
+ * order, no float atomics. */
+typedef enum smhip_reduce_kind {
+    SMHIP_REDUCE_SUM = 0, SMHIP_REDUCE_MEAN = 1, SMHIP_REDUCE_MAX = 2, SMHIP_REDUCE_MIN = 3
+} smhip_reduce_kind;
+/* out = the reduction over the axes set in axes_mask (bit d = axis d) of a[shape, strides] (strides in ELEMENTS, any view,
+ * rank <= SMHIP_MAX_NDIM); `out` is dense row-major over the kept axes in their order, prod(kept extents) elements (1 when
+ * every axis is reduced).  Arguments are checked before any device is touched: kind, dtype, ndim, a mask that is empty or
+ * names an axis >= ndim, negative extents or strides, null pointers.  Asynchronous, stream-ordered. */
+int smhip_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim,
+                      uint32_t axes_mask, void *out);
+/* Host only, no device touched: the route smhip_reduce_axes would take.  *route = a kernel id of the first pass
+ * (SMHIP_REDUCE_ROUTE_*) ORed with the flags below; *launches = the kernel launches of the whole call; ori3 = {O, R, I} of the
+ * first pass after merging (out[o, i] = reduce_r a[o*so + r*sr + i*si]).  Any output may be NULL.  The planner's test hook. */
+#define SMHIP_REDUCE_ROUTE_NONE 0    /* nothing to compute: the result is empty */
+#define SMHIP_REDUCE_ROUTE_ROW 1     /* I = 1, sr = 1: each row of R elements contiguous */
+#define SMHIP_REDUCE_ROUTE_COLUMN 2  /* si = 1: a lane owns 4 consecutive kept columns and walks R */
+#define SMHIP_REDUCE_ROUTE_CHANNEL 3 /* si = 1, sr = I <= 8: the (R, I) block read as one dense stream, I per-channel totals */
+#define SMHIP_REDUCE_ROUTE_FILL 4    /* a sum over an empty extent: zeros */
+#define SMHIP_REDUCE_ROUTE_GATHER 5  /* every reduced extent is 1: the kept elements, copied */
+#define SMHIP_REDUCE_SPLIT 0x100     /* R cut into fixed chunks (the shape decides), partials folded in order by a finishing launch */
+#define SMHIP_REDUCE_COPY 0x200      /* the operand is copied dense first (no unit stride in the walk, a stride-0 axis, ...) */
+#define SMHIP_REDUCE_PASSES 0x400    /* more than one reduced group: one pass per group through an fp64 / T intermediate */
+int smhip_reduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask,
+                      int *route, int *launches, int64_t *ori3);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

@@ -30,6 +30,12 @@ DOT_DTYPES = {**DTYPES, np.dtype(np.int8): I8, np.dtype(np.uint8): U8, np.dtype(
               np.dtype(np.uint32): U32, np.dtype(np.uint64): U64}
 MAX_NDIM = 6
 
+REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = range(4)
+REDUCE_KINDS = {"sum": REDUCE_SUM, "mean": REDUCE_MEAN, "max": REDUCE_MAX, "min": REDUCE_MIN}
+# smhip_reduce_plan's route word: a kernel id in the low byte, flags above it
+ROUTE_NONE, ROUTE_ROW, ROUTE_COLUMN, ROUTE_CHANNEL, ROUTE_FILL, ROUTE_GATHER = range(6)
+ROUTE_SPLIT, ROUTE_COPY, ROUTE_PASSES = 0x100, 0x200, 0x400
+
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
 
@@ -464,6 +470,56 @@ class Smhip:
         out = np.zeros(2, dtype=np.float32)
         self._ck(self.c.smhip_dot_c32(C.c_void_p(a_ptr), C.c_void_p(b_ptr), C.c_size_t(n), out.ctypes.data_as(C.c_void_p)))
         return np.complex64(complex(out[0], out[1]))
+
+    @staticmethod
+    def _axes(ndim, axis):
+        """NumPy's `axis` (an int, a tuple, or None for all) as a sorted tuple of axes; a bad or repeated axis raises."""
+        axes = tuple(range(ndim)) if axis is None else (axis,) if isinstance(axis, (int, np.integer)) else tuple(axis)
+        norm = []
+        for ax in axes:
+            ax = int(ax)
+            if not -ndim <= ax < ndim:
+                raise ValueError(f"axis {ax} is out of bounds for an array of dimension {ndim}")
+            norm.append(ax % ndim)
+        if len(set(norm)) != len(norm):
+            raise ValueError(f"repeated axis in {axis}")
+        return tuple(sorted(norm))
+
+    def reduce(self, kind, a: DeviceArray, axis=None, keepdims=False, out: DeviceArray | None = None):
+        """np.sum / np.mean / np.max / np.min of `a` (any view) over `axis` (int or tuple) -> a new dense DeviceArray, or into
+        `out`, which must be a dense array of a's dtype with as many elements as the result (its shape is not changed).
+        Reducing every axis without keepdims gives shape (1,) (a DeviceArray has no 0-d form)."""
+        kind = REDUCE_KINDS[kind] if isinstance(kind, str) else int(kind)
+        axes = self._axes(a.ndim, axis)
+        mask = sum(1 << d for d in axes)
+        if keepdims:
+            shape = tuple(1 if d in axes else n for d, n in enumerate(a.shape))
+        else:
+            shape = tuple(n for d, n in enumerate(a.shape) if d not in axes) or (1,)
+        if out is None:
+            out = self.empty(shape, a.dtype)
+        elif out.dtype != a.dtype or out.size != int(np.prod(shape, dtype=np.int64)) or not out.is_dense():
+            raise ValueError(f"reduce: out must be a dense {a.dtype} array of {int(np.prod(shape, dtype=np.int64))} elements "
+                             f"(shape {shape}); got {out.dtype} {out.shape} dense={out.is_dense()}")
+        self._ck(self.c.smhip_reduce_axes(C.c_int(kind), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(a.shape), _i64(a.strides),
+                                          C.c_int(a.ndim), C.c_uint32(mask), C.c_void_p(out.ptr)))
+        return out
+
+    def reduce_raw(self, kind, dtype, a_ptr, shape, strides, mask, out_ptr):
+        """smhip_reduce_axes with every argument as given (argument-validation tests)."""
+        return self.c.smhip_reduce_axes(C.c_int(kind), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                        _i64(strides) if strides is not None else None, C.c_int(len(shape) if shape is not None else 0),
+                                        C.c_uint32(mask), C.c_void_p(out_ptr))
+
+    def reduce_plan(self, kind, dtype, shape, strides, axis):
+        """smhip_reduce_plan (host only): (route word, launches, (O, R, I)) for a call on shape / strides (elements) over `axis`."""
+        kind = REDUCE_KINDS[kind] if isinstance(kind, str) else int(kind)
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        axes = self._axes(len(shape), axis)
+        route, launches, ori = C.c_int(0), C.c_int(0), (C.c_int64 * 3)()
+        self._ck(self.c.smhip_reduce_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)),
+                                          C.c_uint32(sum(1 << d for d in axes)), C.byref(route), C.byref(launches), ori))
+        return route.value, launches.value, tuple(int(x) for x in ori)
 
     def sum(self, a: DeviceArray):
         out = C.c_double(0)

@@ -208,5 +208,10 @@ int launch_cdot(const void *a, const void *b, size_t n, double *out2_dev, hipStr
 int launch_cdot32(const void *a, const void *b, size_t n, double *out2_dev, hipStream_t s);  // n {re, im} float pairs; fp64 {re, im} out
 int launch_contiguous_sum(int op, int dtype, const void *a, const void *b, void *out, size_t n, double *sum_dev,
                           hipStream_t s);
+// reduce_axis.hip: axis reductions (smhip_reduce_axes); the checks and the planner are host-only
+int reduce_axes_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask);
+void reduce_axes_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int *route, int *launches, int64_t *ori3);
+int launch_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, void *out,
+                       hipStream_t s);
 
 }  // namespace smhip

@@ -23,6 +23,7 @@
 
 #include "internal.h"
 #include "ops.hip.h"
+#include "wave.hip.h"
 
 namespace smhip {
 namespace {
@@ -48,37 +49,6 @@ constexpr int vec_per_thread(int mode) { return mode == 0 /* kSum */ ? kSumVecto
 
 template <typename T, bool INTEGER = std::is_integral<T>::value> struct AccOf { typedef double type; };
 template <typename T> struct AccOf<T, true> { typedef uint64_t type; };  // wrapping: exact modulo 2^64, hence modulo 2^(8 sizeof T)
-
-// Wave total through DPP moves (v_mov_b32 row_shr / row_bcast: VALU-speed lane exchange inside the SIMD) instead of
-// __shfl_down, which the compiler lowers to ds_bpermute_b32 -- an LDS-crossbar round trip per 32-bit half and stage, with a
-// full lgkmcnt wait behind each: 6 stages x 2 halves for the wave, and round 2 ran the same 6 stages AGAIN in wave 0 to add
-// four numbers.  Every wave of the fused op+sum kernel carried ~1000 cycles of that behind its last store, holding its slot
-// (the kernel ran 2 % behind the plain add: 496-498 us against 486 on one box, tools/sweep_fused2.hip).
-// The scan: row_shr 1, 2, 4, 8 leave each row of 16 lanes' running sum in its lane 15; row_bcast:15 adds it to the next
-// row (rows 1 and 3), row_bcast:31 adds lane 31 to rows 2 and 3: lane 63 holds the wave's total.  Lanes without a source
-// receive `old` = 0, the sum's identity.  The order of the additions is fixed, so the bits are the same on every run
-// (they differ from round 2's tree order in the last place, as any reassociation does).
-constexpr int kWaveTotalLane = 63;
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_move(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ uint64_t dpp_move(uint64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xf, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, 0xf, false);
-    return ((uint64_t)hi << 32) | lo;
-}
-// the wave's total, valid in lane kWaveTotalLane
-template <typename A> __device__ __forceinline__ A wave_reduce(A v) {
-    v += dpp_move<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_move<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_move<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_move<0x118, 0xf>(v);  // row_shr:8
-    v += dpp_move<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-    v += dpp_move<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
-    return v;
-}
 
 // Workgroup total in thread 0: the waves' totals meet in LDS and thread 0 adds them in wave order.
 template <typename A, int BLOCK> __device__ __forceinline__ A block_reduce(A v) {

@@ -1434,6 +1434,23 @@ int smhip_contiguous_sum_async(int op, int dtype, const void *a, const void *b, 
     return launch_contiguous_sum(op, dtype, a, b, out, n, sum_dev, s);
 }
 
+int smhip_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, void *out) {
+    if (int rc = reduce_axes_check("reduce_axes", kind, dtype, shape, strides, ndim, axes_mask)) return rc;
+    int64_t n = 1, nout = 1;
+    for (int d = 0; d < ndim; ++d) n *= shape[d], nout *= (axes_mask >> d & 1) ? 1 : shape[d];
+    if (nout == 0) return SMHIP_OK;
+    if (!out || (n && !a)) return fail(SMHIP_ERR_INVALID, "reduce_axes: null buffer");
+    SMHIP_ACQUIRE(s);  // a reduction: undeclared spans, ordered behind everything (recorded tiny operators flushed first)
+    return launch_reduce_axes(kind, dtype, a, shape, strides, ndim, axes_mask, out, s);
+}
+
+int smhip_reduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int *route, int *launches,
+                      int64_t *ori3) {
+    if (int rc = reduce_axes_check("reduce_plan", kind, dtype, shape, strides, ndim, axes_mask)) return rc;
+    reduce_axes_plan(dtype, shape, strides, ndim, axes_mask, route, launches, ori3);
+    return SMHIP_OK;
+}
+
 int smhip_sum(int dtype, const void *a, size_t n, double *out_host) {
     if (!out_host) return fail(SMHIP_ERR_INVALID, "sum: null result");
     void *h = nullptr, *d = nullptr;

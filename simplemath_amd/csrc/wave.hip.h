@@ -1,0 +1,71 @@
+// wave.hip.h -- in-wave folds through DPP moves, shared by reduce.hip (whole-array reductions) and reduce_axis.hip (axis
+// reductions).
+#pragma once
+
+#include <stdint.h>
+
+#include <type_traits>
+
+namespace smhip {
+namespace dev {
+
+// Wave total through DPP moves (v_mov_b32 row_shr / row_bcast: VALU-speed lane exchange inside the SIMD) instead of
+// __shfl_down, which the compiler lowers to ds_bpermute_b32 -- an LDS-crossbar round trip per 32-bit half and stage, with a
+// full lgkmcnt wait behind each: 6 stages x 2 halves for the wave, and round 2 ran the same 6 stages AGAIN in wave 0 to add
+// four numbers.  Every wave of the fused op+sum kernel carried ~1000 cycles of that behind its last store, holding its slot
+// (the kernel ran 2 % behind the plain add: 496-498 us against 486 on one box, tools/sweep_fused2.hip).
+// The scan: row_shr 1, 2, 4, 8 leave each row of 16 lanes' running sum in its lane 15; row_bcast:15 adds it to the next
+// row (rows 1 and 3), row_bcast:31 adds lane 31 to rows 2 and 3: lane 63 holds the wave's total.  Lanes without a source
+// receive `old` = 0, the sum's identity.  The order of the additions is fixed, so the bits are the same on every run
+// (they differ from round 2's tree order in the last place, as any reassociation does).
+constexpr int kWaveTotalLane = 63;
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_move(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+template <int CTRL, int ROW_MASK> __device__ __forceinline__ uint64_t dpp_move(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, 0xf, false);
+    return ((uint64_t)hi << 32) | lo;
+}
+// the wave's total, valid in lane kWaveTotalLane
+template <typename A> __device__ __forceinline__ A wave_reduce(A v) {
+    v += dpp_move<0x111, 0xf>(v);  // row_shr:1
+    v += dpp_move<0x112, 0xf>(v);  // row_shr:2
+    v += dpp_move<0x114, 0xf>(v);  // row_shr:4
+    v += dpp_move<0x118, 0xf>(v);  // row_shr:8
+    v += dpp_move<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
+    v += dpp_move<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+// The same moves for any 4- or 8-byte value, lanes without a source receiving `old` (the fold's identity).
+template <int CTRL, int ROW_MASK, typename A> __device__ __forceinline__ A dpp_move_or(A v, A old) {
+    static_assert(sizeof(A) == 4 || sizeof(A) == 8, "dpp_move_or: 4- or 8-byte values");
+    if constexpr (sizeof(A) == 4) {
+        const int r = __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, false);
+        return __builtin_bit_cast(A, r);
+    } else {
+        const uint64_t vb = __builtin_bit_cast(uint64_t, v), ob = __builtin_bit_cast(uint64_t, old);
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)ob, (int)(uint32_t)vb, CTRL, ROW_MASK, 0xf, false);
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(ob >> 32), (int)(uint32_t)(vb >> 32), CTRL, ROW_MASK, 0xf, false);
+        return __builtin_bit_cast(A, ((uint64_t)hi << 32) | lo);
+    }
+}
+// wave_reduce's scan, cut short for SEGMENTS of g lanes (g = 1, 2, 4, ..., 64, wave-uniform) and with any associative fold
+// F and its identity: after the row_shr steps up to g / 2, lane i holds the fold of lanes i - g + 1 .. i of its 16-lane row,
+// so the fold of segment s (lanes s*g .. s*g + g - 1) is valid in its LAST lane, s*g + g - 1 (for g = 64: kWaveTotalLane).
+// The order of the operations is fixed: the same bits on every run.
+template <typename A, typename F> __device__ __forceinline__ A segment_fold(A v, int g, A id, F f) {
+    if (g >= 2) v = f(v, dpp_move_or<0x111, 0xf>(v, id));
+    if (g >= 4) v = f(v, dpp_move_or<0x112, 0xf>(v, id));
+    if (g >= 8) v = f(v, dpp_move_or<0x114, 0xf>(v, id));
+    if (g >= 16) v = f(v, dpp_move_or<0x118, 0xf>(v, id));
+    if (g >= 32) v = f(v, dpp_move_or<0x142, 0xa>(v, id));
+    if (g >= 64) v = f(v, dpp_move_or<0x143, 0xc>(v, id));
+    return v;
+}
+
+}  // namespace dev
+}  // namespace smhip
