@@ -781,6 +781,35 @@ public:
         return x.template apply_scalar<PowOp<T>>(value);
     }
 
+    // sm::exp / log / sqrt / abs and unary minus (UserFunctions.h; fn = smhip_unary_fn).  Of the unevaluated temporary of this
+    // full-expression's chain -- sm::exp(x - m), sm::sqrt(a * a + b * b), -(a * row) -- the function is one more stage of that
+    // chain (smhip.h: SMHIP_OP_UNARY_BASE; counted in sm::fusion_stats() like any stage), exactly as pow_of continues it.  Of
+    // anything else -- a named array, a view -- it launches smhip_unary, which reads views in place; the result lives in HBM.
+    static SMArray unary_of(const SMArray &x, bool x_temporary, int fn) {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "sm::exp / log / sqrt / abs / unary minus: f32, f64, i32 and i64 arrays");
+        if (x_temporary) {
+            if (detail::Chain<T> *cx = x.continuable()) {
+                hip::DeviceGuard on(x.device());
+                SMArray out = device_empty(std::vector<std::size_t>(x._shape));
+                detail::Storage<T> &ost = *out.data.storage();
+                ost.pending = std::move(x.data.storage()->pending);
+                cx->retarget(&ost, out._shape);
+                cx->push(SMHIP_OP_UNARY_BASE + fn, false, T{});  // a stage without an operand: the scalar slot, ignored
+                return out;
+            }
+        }
+        hip::DeviceGuard on(x.device());
+        const T *in = x.device_data();  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(std::vector<std::size_t>(x._shape));
+        if (x._shape.empty() || x.totalSize == 0) return out;
+        const auto sh = hip::to_i64(x._shape), st = hip::to_i64(x._strides);
+        hip::check(smhip_unary(fn, hip::dtype_of<T>::id, in, st.data(), sh.data(), static_cast<int>(sh.size()), out.device_data_mut()));
+        return out;
+    }
+    // -a: sign flipped (floats, NaN included) / wrapping negation (integers: -INT_MIN == INT_MIN, as numpy)
+    SMArray operator-() const & { return unary_of(*this, false, SMHIP_UNARY_NEG); }
+    SMArray operator-() && { return unary_of(*this, true, SMHIP_UNARY_NEG); }
+
 private:
     // x Op y (y == nullptr: x Op scalar), recorded rather than launched when it can be part of a one-pass chain: built-in
     // + - * / on an element type with kernels.  See "deferred operator chains" at the top of this file.

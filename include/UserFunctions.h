@@ -44,6 +44,28 @@ SMArray<T> pow(SMArray<T> &&arr, T val) {
     return SMArray<T>::pow_of(arr, true, val);
 }
 
+// Functions of one argument, elementwise (the reference has none: its README names vector exp / log as wanted and missing):
+// e^x, the natural logarithm, the correctly rounded square root, |x|; unary minus is SMArray::operator-.  exp and log are
+// within 1 ULP (smhip.h has the contract table and the special values).  Of a named array or a view they launch one kernel
+// (views are read in place) and the result lives in HBM; of a temporary -- sm::exp(x - m) -- they continue the expression's
+// operator chain like sm::pow(a - b, 2.0f) does, so the difference is never written.
+#define SM_UNARY_FUNCTION(NAME, FN, FLOAT_ONLY)                                                                                    \
+    template <typename T>                                                                                                          \
+    SMArray<T> NAME(const SMArray<T> &arr) {                                                                                       \
+        static_assert(!(FLOAT_ONLY) || std::is_floating_point_v<T>, "sm::" #NAME " is defined for float and double arrays only");  \
+        return SMArray<T>::unary_of(arr, false, FN);                                                                               \
+    }                                                                                                                              \
+    template <typename T>                                                                                                          \
+    SMArray<T> NAME(SMArray<T> &&arr) {                                                                                            \
+        static_assert(!(FLOAT_ONLY) || std::is_floating_point_v<T>, "sm::" #NAME " is defined for float and double arrays only");  \
+        return SMArray<T>::unary_of(arr, true, FN);                                                                                \
+    }
+SM_UNARY_FUNCTION(exp, SMHIP_UNARY_EXP, true)
+SM_UNARY_FUNCTION(log, SMHIP_UNARY_LOG, true)
+SM_UNARY_FUNCTION(sqrt, SMHIP_UNARY_SQRT, true)
+SM_UNARY_FUNCTION(abs, SMHIP_UNARY_ABS, false)
+#undef SM_UNARY_FUNCTION
+
 // Fusion hook: (a Op1 b) Op2 c in ONE pass over HBM (the reference makes two passes and a
 // temporary).  Dense, equal-shaped operands take the two-Op kernel; operands that broadcast against each other (a row, a
 // column, a scalar-like array, the reference tests' (1,224,1,3)) take the chain kernel (smhip_chain) -- what the operators

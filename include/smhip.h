@@ -247,6 +247,39 @@ int smhip_chain_sum_async(int dtype, int n_operands, const void *const *operands
 int smhip_chain_sum(int dtype, int n_operands, const void *const *operands, const int64_t *strides, const void *scalars_host, const int *ops,
                     const int *swapped, const int64_t *shape, int ndim, double *sum_host);
 
+/* ------------------------------------------------ functions of one argument */
+/* out = f(a), elementwise (the reference has none; its README names vector exp / log as wanted and missing).  The contract:
+ *   fn     f32                                f64                 i32 / i64
+ *   NEG    sign bit flipped (NaN included)    the same            wrapping: -INT_MIN == INT_MIN (as numpy)
+ *   ABS    sign bit cleared (NaN included)    the same            wrapping: abs(INT_MIN) == INT_MIN (as numpy)
+ *   SQRT   correctly rounded (IEEE)           correctly rounded   SMHIP_ERR_UNSUPPORTED
+ *   EXP    <= 1 ULP                           <= 1 ULP            SMHIP_ERR_UNSUPPORTED
+ *   LOG    <= 1 ULP (natural logarithm)       <= 1 ULP            SMHIP_ERR_UNSUPPORTED
+ * Special values follow C99 Annex F: exp(-inf) = +0, exp(+inf) = +inf, overflow to +inf, gradual underflow through correct
+ * subnormals to +0; log(+-0) = -inf, log(x < 0) = NaN, log(+inf) = +inf, subnormal arguments handled; sqrt(-0) = -0,
+ * sqrt(x < 0) = NaN; NaN in, NaN out (the payload and sign of a NaN RESULT of sqrt / exp / log are not specified).
+ * Evaluated in registers (csrc/sm_unary.h beside the pow evaluations, whose tables they share); deterministic. */
+typedef enum smhip_unary_fn {
+    SMHIP_UNARY_NEG = 0, SMHIP_UNARY_ABS = 1, SMHIP_UNARY_SQRT = 2, SMHIP_UNARY_EXP = 3, SMHIP_UNARY_LOG = 4
+} smhip_unary_fn;
+/* `a` is any view: `strides` (ELEMENTS, >= 0; 0 broadcasts) over `shape`, rank 1..SMHIP_MAX_NDIM; `out` is dense row-major
+ * over `shape`.  A dense operand moves 2 * sizeof(T) bytes per element; a transposed, stepped or broadcast view is read in
+ * place by NEG / ABS / SQRT (the same traffic) and copied dense first by EXP / LOG (twice the traffic).  out == a is allowed
+ * when `a` is dense (in place); any other overlap of `out` with the operand is SMHIP_ERR_INVALID.  An empty shape is a no-op.
+ * A bad fn, dtype or ndim, a negative extent or stride or a null pointer is SMHIP_ERR_INVALID, checked before any device is
+ * touched, like the integer cells of the table.  Asynchronous, stream-ordered like the other operators; results of <= 4096
+ * elements are not recorded in the tiny batch but run at once, behind everything that is recorded. */
+int smhip_unary(int fn, int dtype, const void *a, const int64_t *strides, const int64_t *shape, int ndim, void *out);
+/* In smhip_chain / smhip_chain_sum / _async a stage may be a function of one argument: ops[k] = SMHIP_OP_UNARY_BASE + fn
+ * applies fn to the chain's value, r = fn(r).  Such a stage takes operands[k + 1] == NULL (anything else is
+ * SMHIP_ERR_INVALID), ignores element k + 1 of scalars_host (scalars_host itself may be NULL when no stage needs it) and
+ * swapped[k], and counts towards SMHIP_CHAIN_MAX_OPERANDS like any other; sqrt / exp / log of an integer dtype is
+ * SMHIP_ERR_UNSUPPORTED.  NEG, ABS, SQRT and the f32 EXP are stages of the one-pass kernel -- sm::exp(x - m),
+ * sm::sqrt(a * a + b * b) move sizeof(T) * (dense operands + 1) bytes per element in one launch; LOG and the f64 EXP (which
+ * look their tables up in LDS) cut the chain like a general pow: they run on the value so far and the chain continues from
+ * the result.  Either way the bits are those of smhip_unary applied to the materialised value. */
+#define SMHIP_OP_UNARY_BASE 16
+
 /* ------------------------------------------------------- axis reductions */
 /* np.sum / np.mean / np.max / np.min over chosen axes (the reference reduces only whole arrays: product.h).  The contract:
  *   kind   f32                                   f64                i32 / i64

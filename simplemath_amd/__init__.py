@@ -31,6 +31,9 @@ DOT_DTYPES = {**DTYPES, np.dtype(np.int8): I8, np.dtype(np.uint8): U8, np.dtype(
 MAX_NDIM = 6
 
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX, REDUCE_MIN = range(4)
+UNARY_NEG, UNARY_ABS, UNARY_SQRT, UNARY_EXP, UNARY_LOG = range(5)  # smhip_unary_fn
+UNARY_FNS = {"neg": UNARY_NEG, "abs": UNARY_ABS, "sqrt": UNARY_SQRT, "exp": UNARY_EXP, "log": UNARY_LOG}
+SMHIP_OP_UNARY_BASE = 16  # a chain stage without an operand: ops[k] = SMHIP_OP_UNARY_BASE + fn
 REDUCE_KINDS = {"sum": REDUCE_SUM, "mean": REDUCE_MEAN, "max": REDUCE_MAX, "min": REDUCE_MIN}
 # smhip_reduce_plan's route word: a kernel id in the low byte, flags above it
 ROUTE_NONE, ROUTE_ROW, ROUTE_COLUMN, ROUTE_CHANNEL, ROUTE_FILL, ROUTE_GATHER = range(6)
@@ -313,11 +316,41 @@ class Smhip:
                                                C.c_void_p(b.ptr), cp, sp, C.c_void_p(out.ptr), C.c_size_t(a.size)))
         return out
 
+    def unary(self, fn, a: DeviceArray, out: DeviceArray | None = None):
+        """out = fn(a), fn one of "neg", "abs", "sqrt", "exp", "log" or the smhip_unary_fn value; `a` any view (read in place by
+        neg / abs / sqrt, copied dense first by exp / log) -> a new dense DeviceArray, or into `out`, which must be a dense array
+        of a's dtype and element count (its shape is not changed); `out` may be `a` itself when `a` is dense (in place)."""
+        fn = UNARY_FNS[fn] if isinstance(fn, str) else int(fn)
+        if out is None:
+            out = self.empty(a.shape, a.dtype)
+        elif out.dtype != a.dtype or out.size != a.size or not out.is_dense():
+            raise ValueError(f"unary: out must be a dense {a.dtype} array of {a.size} elements (shape {tuple(a.shape)}); "
+                             f"got {out.dtype} {out.shape} dense={out.is_dense()}")
+        self._ck(self.c.smhip_unary(C.c_int(fn), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(a.strides), _i64(a.shape),
+                                    C.c_int(a.ndim), C.c_void_p(out.ptr)))
+        return out
+
+    def unary_raw(self, fn, dtype, a_ptr, strides, shape, out_ptr):
+        """smhip_unary with every argument as given (argument-validation tests)."""
+        return self.c.smhip_unary(C.c_int(fn), C.c_int(dtype), C.c_void_p(a_ptr), _i64(strides) if strides is not None else None,
+                                  _i64(shape) if shape is not None else None, C.c_int(len(shape) if shape is not None else 0),
+                                  C.c_void_p(out_ptr))
+
+    @staticmethod
+    def _stage(st):
+        """(op, x, swapped) of a chain stage; a one-element stage -- ("exp",) or (SMHIP_OP_UNARY_BASE + fn,) -- is a function of
+        one argument applied to the chain's value: no operand (x = None)."""
+        if len(st) == 1:
+            op = st[0]
+            return (SMHIP_OP_UNARY_BASE + UNARY_FNS[op] if isinstance(op, str) else int(op), None, False)
+        return (OPS[st[0]] if isinstance(st[0], str) else int(st[0]), st[1], bool(len(st) > 2 and st[2]))
+
     def chain_call(self, first: DeviceArray, *stages, out: DeviceArray | None = None):
         """(callable, out): the prepared smhip_chain call for `chain(first, *stages)` -- timing loops call it without
         paying the argument marshalling again."""
         dt = first.dtype
         shape = list(first.shape)
+        stages = [self._stage(st) for st in stages]
         for st in stages:
             x = st[1]
             if isinstance(x, DeviceArray):
@@ -337,7 +370,8 @@ class Smhip:
             else:
                 strides += [0] * nd
                 ptrs.append(None)
-                scal[k] = x
+                if x is not None:
+                    scal[k] = x
         if out is None:
             out = self.empty(shape, dt)
         ops = (C.c_int * len(stages))(*[int(st[0]) for st in stages])
@@ -357,6 +391,7 @@ class Smhip:
         """(callable -> float): the prepared smhip_chain_sum call for the sum of `chain(first, *stages)`'s value, which is not written."""
         dt = first.dtype
         shape = list(first.shape)
+        stages = [self._stage(st) for st in stages]
         for st in stages:
             x = st[1]
             if isinstance(x, DeviceArray):
@@ -376,7 +411,8 @@ class Smhip:
             else:
                 strides += [0] * nd
                 ptrs.append(None)
-                scal[k] = x
+                if x is not None:
+                    scal[k] = x
         ops = (C.c_int * len(stages))(*[int(st[0]) for st in stages])
         swp = (C.c_int * len(stages))(*[1 if len(st) > 2 and st[2] else 0 for st in stages])
         result = C.c_double(0.0)

@@ -1229,6 +1229,22 @@ int copy_plan(int dtype, const void *src, void *dst, const Plan &pl, hipStream_t
 // the extra launches cost nothing -- and a piece of one outer index recurses into the next dimension.
 constexpr size_t kMaxLaunchElems = 0x7fffffffull;
 
+// The functions of one argument that read a view in place (unary.hip): NEG, ABS and -- float types -- SQRT, as Ops that
+// ignore their right operand (which the caller points at one element, strides 0, like SMHIP_OP_LEFT's).  They take the general
+// kernels (launch_aot) and the pitched-rows kernel; the planes and record kernels are left to the six binary Ops.
+template <typename O> struct OpTag { typedef O type; };
+template <typename T, typename F>
+int unary_through(int op, F &&go) {
+    switch (op - SMHIP_OP_UNARY_BASE) {
+        case SMHIP_UNARY_NEG: return go(OpTag<NegOp<T>>{});
+        case SMHIP_UNARY_ABS: return go(OpTag<AbsOp<T>>{});
+        case SMHIP_UNARY_SQRT:
+            if constexpr (std::is_floating_point<T>::value) return go(OpTag<SqrtOp<T>>{});
+            break;
+    }
+    return fail(SMHIP_ERR_UNSUPPORTED, "elementwise: function %d has no in-place view form for this element type", op - SMHIP_OP_UNARY_BASE);
+}
+
 int launch_plan(int op, int dtype, const void *a, const void *b, void *out, const Plan &pl, hipStream_t s) {
     const bool user = op >= SMHIP_OP_USER_BASE;  // a registered expression: the same kernels, compiled by hipRTC (jit.hip)
     if (pl.ndim == 1) {
@@ -1291,7 +1307,7 @@ int launch_plan(int op, int dtype, const void *a, const void *b, void *out, cons
         const char *e = getenv("SMHIP_PERIODIC_MIN_MIB");
         return (size_t)(e ? atol(e) : 128) << 20;
     }();
-    if (!user && op != SMHIP_OP_LEFT && pl.ndim >= 2 && pl.n * dtype_size(dtype) >= periodic_min_bytes) {
+    if (!user && !left_like(op) && pl.ndim >= 2 && pl.n * dtype_size(dtype) >= periodic_min_bytes) {
         const size_t esz = dtype_size(dtype);
         const int64_t W = 16 / (int64_t)esz;
         for (int role = 0; role < 2; ++role) {
@@ -1370,7 +1386,7 @@ int launch_plan(int op, int dtype, const void *a, const void *b, void *out, cons
         }
     }
     const bool heavy = op == SMHIP_OP_POW && (dtype == SMHIP_F32 || dtype == SMHIP_F64);  // as launch_aot's kRows: float / double pow only
-    if (!user && op != SMHIP_OP_LEFT && pl.ndim == 2 && pl.sa[0] == pl.shape[1] && pl.sa[1] == 1 &&
+    if (!user && !left_like(op) && pl.ndim == 2 && pl.sa[0] == pl.shape[1] && pl.sa[1] == 1 &&
         pl.shape[1] % (16 / (int64_t)dtype_size(dtype)) == 0 &&
         ((pl.sb[0] == 0 && pl.sb[1] == 1) || (pl.sb[0] == 1 && pl.sb[1] == 0 && pl.shape[1] >= SMHIP_FLAT_ROWS_MIN_COLS))) {
         // (one COLUMN against rows of fewer than 16 elements stays with the short-rows kernel: 82 % there, 74-78 % here;
@@ -1486,7 +1502,7 @@ int launch_plan(int op, int dtype, const void *a, const void *b, void *out, cons
     // 46-66 % (tools/short_inner.py); the flat tile kernel's column form takes the whole-vector lengths
     const bool odd_rows = L.kind == Launch::kRow && pl.ndim == 2 && pl.shape[1] >= 16 && pl.shape[1] <= 1024 &&
                           pl.shape[1] % (16 / (int64_t)dtype_size(dtype)) != 0 && pl.n < 0x7fffffffull;
-    if ((odd_rows || (L.kind == Launch::kGather && pl.shape[1] >= 2 && pl.shape[1] < 16)) && pl.ndim == 2 && op != SMHIP_OP_LEFT) {
+    if ((odd_rows || (L.kind == Launch::kGather && pl.shape[1] >= 2 && pl.shape[1] < 16)) && pl.ndim == 2 && !left_like(op)) {
         const bool y_is_b = pl.sa[0] == pl.shape[1] && pl.sa[1] == 1 && pl.sb[0] == 1 && pl.sb[1] == 0;
         const bool y_is_a = pl.sb[0] == pl.shape[1] && pl.sb[1] == 1 && pl.sa[0] == 1 && pl.sa[1] == 0;
         if (y_is_b || y_is_a) {
@@ -1528,6 +1544,7 @@ int launch_plan(int op, int dtype, const void *a, const void *b, void *out, cons
         case SMHIP_OP_DIV: return run_pitched_rows<T, DivideOp<T>>(a, b, out, rows, c, pl.sa[0], pl.sb[0], s);  \
         case SMHIP_OP_POW: return run_pitched_rows<T, PowOp<T>>(a, b, out, rows, c, pl.sa[0], pl.sb[0], s);     \
         case SMHIP_OP_LEFT: return run_pitched_rows<T, LeftOp<T>>(a, b, out, rows, c, pl.sa[0], pl.sb[0], s);   \
+        default: if (unary_op(op)) return unary_through<T>(op, [&](auto f) { return run_pitched_rows<T, typename decltype(f)::type>(a, b, out, rows, c, pl.sa[0], pl.sb[0], s); }); \
     }                                                                                                            \
     break;
         switch (dtype) {
@@ -1546,6 +1563,7 @@ int launch_plan(int op, int dtype, const void *a, const void *b, void *out, cons
         case SMHIP_OP_DIV: return launch_aot<T, DivideOp<T>>(L, a, b, out, s);             \
         case SMHIP_OP_POW: return launch_aot<T, PowOp<T>>(L, a, b, out, s);                \
         case SMHIP_OP_LEFT: return launch_aot<T, LeftOp<T>>(L, a, b, out, s);                \
+        default: if (unary_op(op)) return unary_through<T>(op, [&](auto f) { return launch_aot<T, typename decltype(f)::type>(L, a, b, out, s); }); \
     }                                                                                          \
     break;
     switch (dtype) {

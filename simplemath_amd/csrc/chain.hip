@@ -70,12 +70,54 @@ template <typename T> __device__ __forceinline__ typename VecTraits<T>::full_t s
     return v;
 }
 
-// r = r op x (SWAP: x op r) for one vector; op is wave-uniform
+// r = f(r) for one vector: a stage without an operand (smhip.h: SMHIP_OP_UNARY_BASE + fn; launch_chain only records the ones
+// defined for T); op is wave-uniform
 template <typename T>
+__device__ __forceinline__ typename VecTraits<T>::full_t chain_unary(uint32_t op, typename VecTraits<T>::full_t r) {
+    typedef typename VecTraits<T>::full_t V;
+    constexpr int W = VecTraits<T>::width;
+    V o = r;
+    switch (op) {
+        case SMHIP_OP_UNARY_BASE + SMHIP_UNARY_NEG:
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = NegOp<T>::apply(r[k], r[k]);
+            break;
+        case SMHIP_OP_UNARY_BASE + SMHIP_UNARY_ABS:
+#pragma unroll
+            for (int k = 0; k < W; ++k) o[k] = AbsOp<T>::apply(r[k], r[k]);
+            break;
+        case SMHIP_OP_UNARY_BASE + SMHIP_UNARY_SQRT:
+            if constexpr (std::is_floating_point<T>::value) {
+#pragma unroll
+                for (int k = 0; k < W; ++k) o[k] = SqrtOp<T>::apply(r[k], r[k]);
+            }
+            break;
+        case SMHIP_OP_UNARY_BASE + SMHIP_UNARY_EXP:  // f32 only: no table (sm_unary.h); the W elements side by side, as unary.hip's kernel evaluates them
+            if constexpr (std::is_same<T, float>::value) {
+                float xa[W], xr[W];
+#pragma unroll
+                for (int k = 0; k < W; ++k) xa[k] = r[k];
+                smunary::expf_n<W>(xa, xr);
+#pragma unroll
+                for (int k = 0; k < W; ++k) o[k] = xr[k];
+            }
+            break;
+        default: break;
+    }
+    return o;
+}
+
+// r = r op x (SWAP: x op r) for one vector; op is wave-uniform.  UNARY: the kernel variant for segments that hold a function of
+// one argument -- chains of the binary operators alone keep the kernels they had (with the functions' code in every stage of
+// every kernel, `(a - col) * s` at 8192 x 8192 ran 5 % slower: 78.6 against 74.9 us, same box, alternating).
+template <typename T, bool UNARY>
 __device__ __forceinline__ typename VecTraits<T>::full_t chain_step(uint32_t op, bool swap, typename VecTraits<T>::full_t r,
                                                                     typename VecTraits<T>::full_t x) {
     typedef typename VecTraits<T>::full_t V;
     constexpr int W = VecTraits<T>::width;
+    if constexpr (UNARY) {
+        if (op >= (uint32_t)SMHIP_OP_UNARY_BASE) return chain_unary<T>(op, r);
+    }
     const V lhs = swap ? x : r, rhs = swap ? r : x;
     V o;
     switch (op) {
@@ -101,6 +143,13 @@ __device__ __forceinline__ typename VecTraits<T>::full_t chain_step(uint32_t op,
             break;
     }
     return o;
+}
+
+// Is `op` (a unary stage) one the one-pass kernels evaluate for this dtype?  The others cut the chain (launch_chain).
+inline bool unary_stage_fused(int op, int dtype) {
+    const int fn = op - SMHIP_OP_UNARY_BASE;
+    const bool fp = dtype == SMHIP_F32 || dtype == SMHIP_F64;
+    return fn == SMHIP_UNARY_NEG || fn == SMHIP_UNARY_ABS || (fn == SMHIP_UNARY_SQRT && fp) || (fn == SMHIP_UNARY_EXP && dtype == SMHIP_F32);
 }
 
 // The small operands' vectors for output vector v (v < 2^31: pieces, run_segment).
@@ -139,7 +188,7 @@ __device__ __forceinline__ void chain_small_loads(const ChainArgs<T> &A, uint32_
 // The stages on one vector.  Unrolled: every stage word and scalar sits at a constant offset of the argument block (wide
 // scalar loads up front, in flight with the vector loads); as a run-time loop over byte arrays the stages were three VMEM
 // byte loads each -- a round trip to memory per stage and wave (37.3 us for (A * row + B) * 0.5 at 4096 x 4096).
-template <typename T, int ND, int NR, int NS>
+template <typename T, int ND, int NR, int NS, bool UNARY>
 __device__ __forceinline__ typename VecTraits<T>::full_t chain_eval(const ChainArgs<T> &A, const typename VecTraits<T>::full_t (&d)[ND > 0 ? ND : 1],
                                                                     const typename VecTraits<T>::full_t (&r)[NR > 0 ? NR : 1],
                                                                     const typename VecTraits<T>::full_t (&s)[NS > 0 ? NS : 1]) {
@@ -165,7 +214,7 @@ __device__ __forceinline__ typename VecTraits<T>::full_t chain_eval(const ChainA
     for (int k = 0; k < kMaxStages; ++k) {
         if ((uint32_t)k >= A.n_stages) break;
         const uint32_t w = A.stage[k];
-        acc = chain_step<T>(w & 0xffu, ((w >> 16) & 1u) != 0, acc, pick((w >> 8) & 0xffu, A.scalar[k]));
+        acc = chain_step<T, UNARY>(w & 0xffu, ((w >> 16) & 1u) != 0, acc, pick((w >> 8) & 0xffu, A.scalar[k]));
     }
     return acc;
 }
@@ -173,7 +222,7 @@ __device__ __forceinline__ typename VecTraits<T>::full_t chain_eval(const ChainA
 // One tile of blockDim.x * U vectors per workgroup, no loop over the data.  Full tiles are guard-free: all U x ND streaming
 // loads of a lane go out in one block (inside one arm of the read-policy branch), then the small operands' cached loads,
 // then the stages and the stores.  The last, partial tile and the n % W tail elements take the guarded path.
-template <typename T, int ND, int NR, int NS, int U>
+template <typename T, int ND, int NR, int NS, int U, bool UNARY>
 __global__ __launch_bounds__(1024) void chain_kernel(ChainArgs<T> A, T *__restrict__ out, size_t n_vec, int tail, int pol) {
     typedef typename VecTraits<T>::vec_t V;
     typedef typename VecTraits<T>::full_t F;
@@ -197,7 +246,7 @@ __global__ __launch_bounds__(1024) void chain_kernel(ChainArgs<T> A, T *__restri
         for (int u = 0; u < U; ++u) chain_small_loads<T, NR, NS>(A, (uint32_t)(base + (size_t)u * blockDim.x), r[u], s[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const F acc = chain_eval<T, ND, NR, NS>(A, d[u], r[u], s[u]);
+            const F acc = chain_eval<T, ND, NR, NS, UNARY>(A, d[u], r[u], s[u]);
             store_stream_if(T, reinterpret_cast<V *>(out) + base + (size_t)u * blockDim.x, acc, pol);
         }
         return;
@@ -214,7 +263,7 @@ __global__ __launch_bounds__(1024) void chain_kernel(ChainArgs<T> A, T *__restri
                 for (int e = 0; e < W; ++e) d[k][e] = e < tail ? A.dense[k][n_vec * W + e] : T{};  // the lane past the body: element by element
         }
         chain_small_loads<T, NR, NS>(A, (uint32_t)i, r, s);
-        const F acc = chain_eval<T, ND, NR, NS>(A, d, r, s);
+        const F acc = chain_eval<T, ND, NR, NS, UNARY>(A, d, r, s);
         if (body) store_stream(reinterpret_cast<V *>(out) + i, acc);
         else
             for (int e = 0; e < tail; ++e) out[n_vec * W + e] = acc[e];
@@ -239,7 +288,7 @@ template <int CTRL, int ROW_MASK, typename A> __device__ __forceinline__ A chain
     return __builtin_bit_cast(A, ((unsigned long long)hi << 32) | lo);
 }
 constexpr int kChainSumBlock = 256, kChainSumU = 4;  // vectors per lane: a quarter of the partials, and a lane's loads all in flight together
-template <typename T, int ND>
+template <typename T, int ND, bool UNARY>
 __global__ __launch_bounds__(kChainSumBlock) void chain_sum_kernel(ChainArgs<T> A, typename ChainAcc<T>::type *__restrict__ partials, size_t n_vec, int tail, int pol) {
     typedef typename VecTraits<T>::vec_t V;
     typedef typename VecTraits<T>::full_t F;
@@ -263,7 +312,7 @@ __global__ __launch_bounds__(kChainSumBlock) void chain_sum_kernel(ChainArgs<T> 
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const F v = chain_eval<T, ND, 0, 0>(A, d[u], r, s);
+            const F v = chain_eval<T, ND, 0, 0, UNARY>(A, d[u], r, s);
 #pragma unroll
             for (int e = 0; e < W; ++e) acc += chain_widen<T, Acc>(v[e]);
         }
@@ -274,14 +323,14 @@ __global__ __launch_bounds__(kChainSumBlock) void chain_sum_kernel(ChainArgs<T> 
             if (i < n_vec) {
 #pragma unroll
                 for (int k = 0; k < ND; ++k) d[k] = load_stream(reinterpret_cast<const V *>(A.dense[k]) + i);
-                const F v = chain_eval<T, ND, 0, 0>(A, d, r, s);
+                const F v = chain_eval<T, ND, 0, 0, UNARY>(A, d, r, s);
 #pragma unroll
                 for (int e = 0; e < W; ++e) acc += chain_widen<T, Acc>(v[e]);
             } else if (i == n_vec && tail) {  // the n % W elements past the last whole vector
 #pragma unroll
                 for (int k = 0; k < ND; ++k)
                     for (int e = 0; e < W; ++e) d[k][e] = e < tail ? A.dense[k][n_vec * W + e] : T(1);
-                const F v = chain_eval<T, ND, 0, 0>(A, d, r, s);
+                const F v = chain_eval<T, ND, 0, 0, UNARY>(A, d, r, s);
                 for (int e = 0; e < tail; ++e) acc += chain_widen<T, Acc>(v[e]);
             }
         }
@@ -368,13 +417,13 @@ LeafKind classify(const Problem &pb, const int64_t *strides, uint64_t *P, uint64
     return kComplex;
 }
 
-template <typename T, int U>
+template <typename T, int U, bool UNARY>
 int launch_variant_u(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t n_vec, int tail, int pol, int block, hipStream_t s) {
     const size_t tiles = n_vec / ((size_t)block * U) + 1;  // the last workgroup: partial tile + tail elements (maybe empty)
     if (tiles > 0x7fffffffu) return fail(SMHIP_ERR_UNSUPPORTED, "chain: array too large for one launch");
     const dim3 grid((unsigned)tiles), blk(block);
 #define SMHIP_CHAIN_CASE(ND, NR, NS) \
-    case (ND) * 9 + (NR) * 3 + (NS): hipLaunchKernelGGL((chain_kernel<T, ND, NR, NS, U>), grid, blk, 0, s, A, out, n_vec, tail, pol); break;
+    case (ND) * 9 + (NR) * 3 + (NS): hipLaunchKernelGGL((chain_kernel<T, ND, NR, NS, U, UNARY>), grid, blk, 0, s, A, out, n_vec, tail, pol); break;
 #define SMHIP_CHAIN_SMALL(ND) \
     SMHIP_CHAIN_CASE(ND, 0, 1) SMHIP_CHAIN_CASE(ND, 0, 2) SMHIP_CHAIN_CASE(ND, 1, 0) SMHIP_CHAIN_CASE(ND, 1, 1) SMHIP_CHAIN_CASE(ND, 1, 2) \
     SMHIP_CHAIN_CASE(ND, 2, 0) SMHIP_CHAIN_CASE(ND, 2, 1) SMHIP_CHAIN_CASE(ND, 2, 2)
@@ -393,7 +442,7 @@ int launch_variant_u(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size
 }
 
 template <typename T>
-int launch_variant(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t n_vec, int tail, int pol, hipStream_t s) {
+int launch_variant(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t n_vec, int tail, int pol, bool unary, hipStream_t s) {
     static const int forced_block = [] { const char *e = getenv("SMHIP_CHAIN_BLOCK"); return e && *e ? atoi(e) : 0; }();  // experiments
     static const int forced_u = [] { const char *e = getenv("SMHIP_CHAIN_U"); return e && *e ? atoi(e) : 0; }();
     // workgroups of 256, one vector per lane: (A * row + B) * 0.5 at 4096 x 4096 29.9 us (84 % of peak on its 12 B/elem) against
@@ -407,8 +456,9 @@ int launch_variant(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t
     const int block = clamp_ok ? forced_block : (ns == 0 && n_vec <= ((size_t)1 << 24) ? 512 : 256);
     (void)nd;
     const int u = forced_u ? forced_u : 1;
-    if (u == 2) return launch_variant_u<T, 2>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
-    return launch_variant_u<T, 1>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
+    if (unary) return launch_variant_u<T, 1, true>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);  // (one vector per lane only)
+    if (u == 2) return launch_variant_u<T, 2, false>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
+    return launch_variant_u<T, 1, false>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
 }
 
 // A few items in place: planning a chain allocates nothing (a chain call on a 4 MB array is host-bound: every 100 ns of
@@ -474,7 +524,9 @@ int run_segment(const Problem &pb, const Segment &sg, void *out_, hipStream_t s)
     if (head_slot < 0) return fail(SMHIP_ERR_INVALID, "chain: segment head has no operand slot");
     A.head = (uint32_t)head_slot;
     A.n_stages = (uint32_t)sg.ops.size();
+    bool unary = false;
     for (size_t k = 0; k < sg.ops.size(); ++k) {
+        unary = unary || unary_op(sg.ops[k]);
         const int slot = slot_of(sg.leaves[k + 1], (int)k);
         if (slot < 0) return fail(SMHIP_ERR_INVALID, "chain: a segment with more operands than its kernel variant takes (stage %zu)", k);  // the planner's bug, never the GPU's problem
         A.stage[k] = (uint32_t)sg.ops[k] | (uint32_t)slot << 8 | (uint32_t)(sg.swaps[k] ? 1 : 0) << 16;
@@ -514,7 +566,7 @@ int run_segment(const Problem &pb, const Segment &sg, void *out_, hipStream_t s)
             static const bool uniform_ok = [] { const char *e = getenv("SMHIP_CHAIN_UNIFORM_SPLAT"); return !(e && *e && atoi(e) == 0); }();
             if (!elem && uniform_ok && r % 64 == 0 && A.spl_r0[k] % 64 == 0) A.spl_elem[k] = 2;
         }
-        if (int rc = launch_variant<T>(nd, nr, ns, A, out + v0 * W, nv, last ? tail : 0, pol, s)) return rc;
+        if (int rc = launch_variant<T>(nd, nr, ns, A, out + v0 * W, nv, last ? tail : 0, pol, unary, s)) return rc;
         if (last) break;
     }
     return SMHIP_OK;
@@ -642,8 +694,8 @@ int try_chain_sum(const Problem &pb, int n_operands, const void *const *operands
     Few<Span, kMaxDense> reads;
     auto slot_of = [&](int k, int stage) -> int {
         if (!operands[k]) {
-            if (stage >= 0) memcpy(&A.scalar[stage], static_cast<const char *>(scalars_host) + (size_t)k * sizeof(T), sizeof(T));
-            return kSlotScalar;
+            if (stage >= 0 && !unary_op(ops[stage])) memcpy(&A.scalar[stage], static_cast<const char *>(scalars_host) + (size_t)k * sizeof(T), sizeof(T));
+            return kSlotScalar;  // (a stage without an operand reads no scalar: its slot stays zero)
         }
         uint64_t P, R, C;
         bool writeout;
@@ -659,12 +711,15 @@ int try_chain_sum(const Problem &pb, int n_operands, const void *const *operands
     if (head < 0 || head == kSlotScalar) return SMHIP_OK;
     A.head = (uint32_t)head;
     A.n_stages = (uint32_t)n_stages;
+    bool unary = false;
     for (int k = 0; k < n_stages; ++k) {
+        unary = unary || unary_op(ops[k]);
         if (ops[k] == SMHIP_OP_POW) {  // only the square is a stage (launch_chain)
             T e;
             memcpy(&e, static_cast<const char *>(scalars_host) + (size_t)(k + 1) * sizeof(T), sizeof(T));
             if (operands[k + 1] || swapped[k] || !(e == T(2))) return SMHIP_OK;
         }
+        if (unary_op(ops[k]) && !unary_stage_fused(ops[k], pb.dtype)) return SMHIP_OK;  // LOG, f64 EXP: not a stage of this kernel
         const int slot = slot_of(k + 1, k);
         if (slot < 0) return SMHIP_OK;
         A.stage[k] = (uint32_t)ops[k] | (uint32_t)slot << 8 | (uint32_t)(swapped[k] ? 1 : 0) << 16;
@@ -696,11 +751,20 @@ int try_chain_sum(const Problem &pb, int n_operands, const void *const *operands
         for (int k = 0; k < nd; ++k) A.dense[k] = dense0[k] + v0 * W;
         Acc *part = partials + v0 / kTile;
         if (blocks) {
-            switch (nd) {
-                case 1: hipLaunchKernelGGL((chain_sum_kernel<T, 1>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
-                case 2: hipLaunchKernelGGL((chain_sum_kernel<T, 2>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
-                case 3: hipLaunchKernelGGL((chain_sum_kernel<T, 3>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
-                default: hipLaunchKernelGGL((chain_sum_kernel<T, 4>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+            if (unary) {
+                switch (nd) {
+                    case 1: hipLaunchKernelGGL((chain_sum_kernel<T, 1, true>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                    case 2: hipLaunchKernelGGL((chain_sum_kernel<T, 2, true>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                    case 3: hipLaunchKernelGGL((chain_sum_kernel<T, 3, true>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                    default: hipLaunchKernelGGL((chain_sum_kernel<T, 4, true>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                }
+            } else {
+                switch (nd) {
+                    case 1: hipLaunchKernelGGL((chain_sum_kernel<T, 1, false>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                    case 2: hipLaunchKernelGGL((chain_sum_kernel<T, 2, false>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                    case 3: hipLaunchKernelGGL((chain_sum_kernel<T, 3, false>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                    default: hipLaunchKernelGGL((chain_sum_kernel<T, 4, false>), dim3((unsigned)blocks), dim3(kChainSumBlock), 0, s, A, part, nv, tl, pol); break;
+                }
             }
             SMHIP_LAUNCH_CHECK("chain_sum_kernel");
         }
@@ -745,7 +809,7 @@ int launch_chain(int dtype, int n_operands, const void *const *operands, const i
         Leaf &lf = leaves[k];
         if (!operands[k]) {
             lf.kind = kScalar;
-            memcpy(lf.scalar, static_cast<const char *>(scalars_host) + (size_t)k * pb.esz, pb.esz);
+            if (!(k > 0 && unary_op(ops[k - 1]))) memcpy(lf.scalar, static_cast<const char *>(scalars_host) + (size_t)k * pb.esz, pb.esz);
             continue;
         }
         lf.ptr = operands[k];
@@ -879,6 +943,32 @@ int launch_chain(int dtype, int n_operands, const void *const *operands, const i
             void *buf = last ? out : nullptr;
             if (!buf) if (int rc = temps.take(pb.n * pb.esz, &buf)) return rc;
             if (int rc = launch_array_scalar(SMHIP_OP_POW, dtype, cur->ptr, x->scalar, pb.n, buf, s)) return rc;
+            if (last) return SMHIP_OK;
+            start(new_temp_head(buf));
+            continue;
+        }
+        if (unary_op(ops[k])) {
+            // r = f(r).  NEG, ABS, SQRT and the f32 EXP are stages of the one-pass kernel (their "operand" is the scalar slot,
+            // which they ignore); LOG and the f64 EXP look tables up in LDS, which chain_kernel does not stage: they cut the
+            // chain like a general pow above and run unary.hip's kernel on the value so far -- the same bits either way.
+            const bool head_view = sg.ops.empty() && h->kind == kComplex;  // a transposed / stepped view with nothing applied yet
+            if (unary_stage_fused(ops[k], dtype) && !head_view) {
+                if ((int)sg.ops.size() == kMaxStages) {
+                    const Leaf *cur;
+                    if (int rc = emit(nullptr, &cur)) return rc;
+                    start(cur);
+                }
+                sg.leaves.push_back(x);
+                sg.ops.push_back(ops[k]);
+                sg.swaps.push_back(0);
+                continue;
+            }
+            const Leaf *cur;
+            if (int rc = emit(nullptr, &cur)) return rc;  // the value so far (a head with nothing applied: as it is)
+            void *buf = last ? out : nullptr;
+            if (!buf) if (int rc = temps.take(pb.n * pb.esz, &buf)) return rc;
+            const Leaf *src = original_of(cur);
+            if (int rc = launch_unary(ops[k] - SMHIP_OP_UNARY_BASE, dtype, src->ptr, src->strides, pb.full_shape, pb.full_ndim, buf, s)) return rc;
             if (last) return SMHIP_OK;
             start(new_temp_head(buf));
             continue;

@@ -606,6 +606,8 @@ int run_devscalar(const void *a, const void *sp, size_t n, void *out, hipStream_
     return SMHIP_OK;
 }
 
+template <typename O> struct UnaryTag { typedef O type; };
+
 // op x dtype dispatch: F(T, Op) expands to a call.
 #define SMHIP_DISPATCH_OP(T, F)                                  \
     switch (op) {                                                \
@@ -651,6 +653,27 @@ int launch_array_scalar(int op, int dtype, const void *a, const void *value_host
     SMHIP_DISPATCH(F)
 #undef F
     return fail(SMHIP_ERR_INVALID, "array_scalar: bad op %d / dtype %d", op, dtype);
+}
+
+// exp / log with a table in LDS (unary.hip: the f32 log, the f64 exp and log) through pow's one-shot tile form -- several
+// vectors per lane, so that a workgroup stages the table once per 8-12 KiB of data instead of once per 4 KiB, and the table's
+// reads are in flight together with the data's (flat_tile_kernel: fetch / commit).  The Op ignores its second operand.
+int launch_unary_tiles(int fn, int dtype, const void *a, size_t n, void *out, hipStream_t s) {
+    if (n == 0) return SMHIP_OK;
+    auto go = [&](auto op_tag, auto zero) -> int {
+        typedef decltype(zero) T;
+        typedef typename decltype(op_tag)::type Op;
+        constexpr int W = VecTraits<T>::width;
+        const size_t n_vec = n / W;
+        if (n_vec / ((size_t)kTileBlock * 2) + 1 > 0x7fffffffu) return fail(SMHIP_ERR_UNSUPPORTED, "array too large for one launch");
+        launch_heavy<T, Op, 1>(static_cast<const T *>(a), static_cast<const T *>(nullptr), T{}, static_cast<T *>(out), n_vec, (int)(n % W), s);
+        SMHIP_LAUNCH_CHECK("unary (tile form)");
+        return SMHIP_OK;
+    };
+    if (dtype == SMHIP_F32 && fn == SMHIP_UNARY_LOG) return go(UnaryTag<LogOp<float>>{}, 0.0f);
+    if (dtype == SMHIP_F64 && fn == SMHIP_UNARY_EXP) return go(UnaryTag<ExpOp<double>>{}, 0.0);
+    if (dtype == SMHIP_F64 && fn == SMHIP_UNARY_LOG) return go(UnaryTag<LogOp<double>>{}, 0.0);
+    return fail(SMHIP_ERR_INVALID, "unary (tile form): function %d / dtype %d has no table", fn, dtype);
 }
 
 int launch_array_devscalar(int op, int dtype, const void *a, const void *value_dev, size_t n, void *out, bool swapped,

@@ -179,6 +179,14 @@ int launch_inline(int op, int dtype, const void *a, size_t a_host_bytes, const i
                   const int64_t *sb, const int64_t *shape, int ndim, void *out, hipStream_t s);
 int launch_copy_strided(int dtype, const void *src, const int64_t *src_strides, void *dst, const int64_t *dst_strides,
                         const int64_t *shape, int ndim, hipStream_t s);
+// unary.hip: out = f(a), f = smhip_unary_fn.  _dense: n dense elements, out may be a; the other reads any view in place
+// (NEG / ABS / SQRT through the broadcast kernels) or copies it into `out` first (EXP / LOG).  `out` dense over `shape`.
+int launch_unary_dense(int fn, int dtype, const void *a, size_t n, void *out, hipStream_t s);
+int launch_unary_tiles(int fn, int dtype, const void *a, size_t n, void *out, hipStream_t s);  // contiguous.hip: the functions with a table in LDS
+int launch_unary(int fn, int dtype, const void *a, const int64_t *strides, const int64_t *shape, int ndim, void *out, hipStream_t s);
+inline bool unary_op(int op) { return op >= SMHIP_OP_UNARY_BASE && op <= SMHIP_OP_UNARY_BASE + SMHIP_UNARY_LOG; }
+// an Op that reads its left operand only: the copy and the functions of one argument the broadcast kernels serve
+inline bool left_like(int op) { return op == SMHIP_OP_LEFT || unary_op(op); }
 // run-time compiled user Ops (jit.hip)
 int jit_register(const char *expr, int *op_id);
 int jit_fused_expr(const char *expr, int dtype, const void *const *operands, int n_operands, const void *scalars_host, int n_scalars,

@@ -18,6 +18,7 @@
 
 #include "sm_pow.h"
 #include "sm_pow64.h"
+#include "sm_unary.h"
 
 namespace smhip {
 namespace dev {
@@ -221,6 +222,28 @@ template <> struct PowOp<double> {
     static __device__ __forceinline__ double apply(double a, double b) { return smpow64::pow(a, b, smpow64::kLogTab, smpow64::kExpTab); }
 };
 
+// ------------------------------------------------------- functions of one argument (smhip_unary, SMHIP_OP_UNARY_BASE + fn)
+// Binary-shaped on purpose -- apply(a, b) ignores b, like LeftOp -- so that the broadcast kernels read a VIEW in place for
+// them and the chain kernel takes them as stages without an operand.  NEG / ABS work on the bits (the sign of a NaN
+// included; integers wrap: -INT_MIN == INT_MIN, as numpy); SQRT is the correctly rounded IEEE square root (the compiler's
+// expansion around v_sqrt_f32 / v_rsq_f64 with its fix-up steps, not the bare instruction); EXP / LOG are sm_unary.h's.
+template <typename T> struct NegOp { static __device__ __forceinline__ T apply(T a, T) { typedef typename UInt<T>::type U; return (T)((U)0 - (U)a); } };
+template <typename T> struct AbsOp { static __device__ __forceinline__ T apply(T a, T) { typedef typename UInt<T>::type U; return a < 0 ? (T)((U)0 - (U)a) : a; } };
+template <> struct NegOp<float> { static __device__ __forceinline__ float apply(float a, float) { return smpow::bits_f32(smpow::f32_bits(a) ^ 0x80000000u); } };
+template <> struct AbsOp<float> { static __device__ __forceinline__ float apply(float a, float) { return smpow::bits_f32(smpow::f32_bits(a) & 0x7fffffffu); } };
+template <> struct NegOp<double> { static __device__ __forceinline__ double apply(double a, double) { return smpow::bits_f64(smpow::f64_bits(a) ^ 0x8000000000000000ULL); } };
+template <> struct AbsOp<double> { static __device__ __forceinline__ double apply(double a, double) { return smpow::bits_f64(smpow::f64_bits(a) & 0x7fffffffffffffffULL); } };
+template <typename T> struct SqrtOp;
+template <> struct SqrtOp<float> { static __device__ __forceinline__ float apply(float a, float) { return __builtin_sqrtf(a); } };
+template <> struct SqrtOp<double> { static __device__ __forceinline__ double apply(double a, double) { return __builtin_sqrt(a); } };
+// the scalar forms read their tables from constant memory; the vector kernels from LDS copies (OpCtx below)
+template <typename T> struct ExpOp;
+template <> struct ExpOp<float> { static __device__ __forceinline__ float apply(float a, float) { return smunary::expf(a); } };
+template <> struct ExpOp<double> { static __device__ __forceinline__ double apply(double a, double) { return smunary::exp(a); } };
+template <typename T> struct LogOp;
+template <> struct LogOp<float> { static __device__ __forceinline__ float apply(float a, float) { return smunary::logf(a); } };
+template <> struct LogOp<double> { static __device__ __forceinline__ double apply(double a, double) { return smunary::log(a); } };
+
 // Per-workgroup state an Op may need.  Kernels create one and call init() at
 // their top, before any early exit (init may contain a barrier).  Only
 // PowOp<float> has any: its 752-byte log2 breakpoint table, staged from
@@ -297,6 +320,13 @@ template <> struct OpCtx<PowOp<double>> {
         exptab = lds_tab + smpow64::kLogTabDoubles;
     }
 };
+
+// LogOp<float> looks its intervals up in PowOp<float>'s table; ExpOp<double> / LogOp<double> in PowOp<double>'s (the exp
+// half reads only the 2 KiB {T, tail} part, the log half only the 3 KiB {invc, logc, tail} part, but one staging routine
+// serves both: 5 KiB per workgroup leaves the occupancy where it was).  ExpOp<float> needs no table at all.
+template <> struct OpCtx<LogOp<float>> : OpCtx<PowOp<float>> {};
+template <> struct OpCtx<ExpOp<double>> : OpCtx<PowOp<double>> {};
+template <> struct OpCtx<LogOp<double>> : OpCtx<PowOp<double>> {};
 
 // PowOp<double> for the flat tile kernel: the same arithmetic reading its tables from BANK-PRIVATE replicas (sm_pow64.h:
 // TabBanked), so that a wave's scattered lookups never collide.  Round 2's scalar-exponent kernel spent 43 % of its
@@ -397,6 +427,14 @@ __device__ __forceinline__ void apply_n(const OpCtx<Op> &ctx, const T (&a)[W], c
         smpow::pow_n<W>(a, b, r, ctx.tab);
     } else if constexpr (std::is_same<Op, PowOp<double>>::value) {
         smpow64::pow_n<W>(a, b, r, ctx.logtab, ctx.exptab);
+    } else if constexpr (std::is_same<Op, ExpOp<float>>::value) {
+        smunary::expf_n<W>(a, r);
+    } else if constexpr (std::is_same<Op, LogOp<float>>::value) {
+        smunary::logf_n<W>(a, r, ctx.tab);
+    } else if constexpr (std::is_same<Op, ExpOp<double>>::value) {
+        smunary::exp_n<W>(a, r, smpow64::TabAoS{ctx.logtab, ctx.exptab});
+    } else if constexpr (std::is_same<Op, LogOp<double>>::value) {
+        smunary::log_n<W>(a, r, smpow64::TabAoS{ctx.logtab, ctx.exptab});
     } else if constexpr (std::is_same<Op, PowBanked>::value) {
         smpow64::pow_n<W, smpow64::TabBanked>(a, b, r, ctx.tab);
     } else if constexpr (HalfIntOf<Op>::value != 0) {

@@ -1359,6 +1359,7 @@ int check_chain(const char *who, int dtype, int n_operands, const void *const *o
     }
     for (int k = 0; k < n_operands; ++k) {
         if (!operands[k]) {
+            if (k > 0 && unary_op(ops[k - 1])) continue;  // the empty operand of a function of one argument: no scalar is read
             if (!scalars_host) return fail(SMHIP_ERR_INVALID, "%s: operand %d is a scalar but scalars_host is NULL", who, k);
             continue;
         }
@@ -1370,7 +1371,13 @@ int check_chain(const char *who, int dtype, int n_operands, const void *const *o
             if (operands[k + 1] || swapped[k]) return fail(SMHIP_ERR_UNSUPPORTED, "%s: pow (stage %d) takes the chain's value to a SCALAR power", who, k);
             continue;
         }
-        if (ops[k] < SMHIP_OP_ADD || ops[k] > SMHIP_OP_DIV) return fail(SMHIP_ERR_UNSUPPORTED, "%s: op %d (stage %d) is not one of add, sub, mul, div, pow", who, ops[k], k);
+        if (unary_op(ops[k])) {  // r = f(r): no operand
+            if (operands[k + 1]) return fail(SMHIP_ERR_INVALID, "%s: stage %d is a function of one argument and takes no operand (operands[%d] must be NULL)", who, k, k + 1);
+            if (ops[k] - SMHIP_OP_UNARY_BASE >= SMHIP_UNARY_SQRT && (dtype == SMHIP_I32 || dtype == SMHIP_I64))
+                return fail(SMHIP_ERR_UNSUPPORTED, "%s: sqrt / exp / log (stage %d) of an integer element type", who, k);
+            continue;
+        }
+        if (ops[k] < SMHIP_OP_ADD || ops[k] > SMHIP_OP_DIV) return fail(SMHIP_ERR_UNSUPPORTED, "%s: op %d (stage %d) is not one of add, sub, mul, div, pow or a function of one argument", who, ops[k], k);
     }
     *n_out = n;
     return SMHIP_OK;
