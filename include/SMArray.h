@@ -90,6 +90,7 @@ struct FusionStats {
     unsigned long long direct_assignments = 0;  // `x = <expression>` evaluated straight into x (no temporary, no copy)
     unsigned long long summed_chains = 0;       // `(<expression>).sum()` taken in the chain's own pass, the value never written
     unsigned long long reductions = 0;          // axis reductions (smhip_reduce_axes: sum / mean / max / min along axes)
+    unsigned long long scans = 0;               // cumulative scans (smhip_scan_axis: cumsum / cumprod / cummax / cummin)
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -724,6 +725,23 @@ public:
     SMArray min(int axis, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_MIN, {axis}, keepdims); }
     SMArray min(std::initializer_list<int> axes, bool keepdims = false) const { return reduce_along(SMHIP_REDUCE_MIN, axes, keepdims); }
 
+    // Cumulative scans ALONG AN AXIS (np.cumsum / np.cumprod / np.maximum.accumulate / np.minimum.accumulate): the result has
+    // the shape of this array, element r along `axis` holding the fold of elements 0 .. r, resident on the device.
+    //   cumsum / cumprod   f32: the running value held in fp64, each output rounded once; f64: fp64; integers: wrapping in T
+    //   cummax / cummin    exact; from a NaN on, every later output along the axis is NaN
+    // `axis` counts from the end when negative; an axis out of range throws std::runtime_error.  Without an axis the elements
+    // are scanned in row-major order and the result has shape {totalSize}, as np.cumsum(a) does.  A pending operator chain as
+    // the operand is evaluated first; the scan is ONE smhip_scan_axis call (counted in sm::fusion_stats().scans) and its
+    // result feeds the next chain like any array: `h.cumsum(0) / h.sum(0, true)` is a CDF.
+    SMArray cumsum(int axis) const { return scan_along(SMHIP_SCAN_SUM, axis); }
+    SMArray cumprod(int axis) const { return scan_along(SMHIP_SCAN_PROD, axis); }
+    SMArray cummax(int axis) const { return scan_along(SMHIP_SCAN_MAX, axis); }
+    SMArray cummin(int axis) const { return scan_along(SMHIP_SCAN_MIN, axis); }
+    SMArray cumsum() const { return scan_flat(SMHIP_SCAN_SUM); }
+    SMArray cumprod() const { return scan_flat(SMHIP_SCAN_PROD); }
+    SMArray cummax() const { return scan_flat(SMHIP_SCAN_MAX); }
+    SMArray cummin() const { return scan_flat(SMHIP_SCAN_MIN); }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -961,6 +979,32 @@ private:
         const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
         hip::check(smhip_reduce_axes(kind, hip::dtype_of<T>::id, in, sh.data(), st.data(), nd, mask, out.device_data_mut()));
         ++detail::tls_fusion_stats.reductions;
+        return out;
+    }
+
+    SMArray scan_along(int kind, int axis) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "cumulative scans: f32, f64, i32 and i64");
+        const int nd = static_cast<int>(_shape.size());
+        const int a = axis < 0 ? axis + nd : axis;
+        if (a < 0 || a >= nd) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(axis) + " out of range for rank " + std::to_string(nd));
+        hip::DeviceGuard on(device());
+        const T *in = device_data();  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(std::vector<std::size_t>(_shape));
+        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
+        hip::check(smhip_scan_axis(kind, hip::dtype_of<T>::id, in, sh.data(), st.data(), nd, a, out.device_data_mut()));
+        ++detail::tls_fusion_stats.scans;
+        return out;
+    }
+    // The elements in row-major order as one row: a view is made dense first.
+    SMArray scan_flat(int kind) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "cumulative scans: f32, f64, i32 and i64");
+        hip::DeviceGuard on(device());
+        std::unique_ptr<SMArray> holder;
+        const T *in = dense_device(holder);
+        SMArray out = device_empty(std::vector<std::size_t>{totalSize});
+        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
+        hip::check(smhip_scan_axis(kind, hip::dtype_of<T>::id, in, &n, &one, 1, 0, out.device_data_mut()));
+        ++detail::tls_fusion_stats.scans;
         return out;
     }
 

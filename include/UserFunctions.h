@@ -225,6 +225,26 @@ SMArray<T> min(const SMArray<T> &arr, int axis, bool keepdims = false) { return 
 template <typename T>
 SMArray<T> min(const SMArray<T> &arr, std::initializer_list<int> axes, bool keepdims = false) { return arr.min(axes, keepdims); }
 
+// Cumulative scans (np.cumsum / np.cumprod / np.maximum.accumulate / np.minimum.accumulate): the result has the shape of
+// `arr`; `axis` counts from the end when negative; without an axis the elements are scanned in row-major order and the
+// result has shape {size}.  Semantics as SMArray::cumsum(axis) (SMArray.h) and smhip_scan_axis (smhip.h).
+template <typename T>
+SMArray<T> cumsum(const SMArray<T> &arr, int axis) { return arr.cumsum(axis); }
+template <typename T>
+SMArray<T> cumsum(const SMArray<T> &arr) { return arr.cumsum(); }
+template <typename T>
+SMArray<T> cumprod(const SMArray<T> &arr, int axis) { return arr.cumprod(axis); }
+template <typename T>
+SMArray<T> cumprod(const SMArray<T> &arr) { return arr.cumprod(); }
+template <typename T>
+SMArray<T> cummax(const SMArray<T> &arr, int axis) { return arr.cummax(axis); }
+template <typename T>
+SMArray<T> cummax(const SMArray<T> &arr) { return arr.cummax(); }
+template <typename T>
+SMArray<T> cummin(const SMArray<T> &arr, int axis) { return arr.cummin(axis); }
+template <typename T>
+SMArray<T> cummin(const SMArray<T> &arr) { return arr.cummin(); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

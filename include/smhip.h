@@ -316,6 +316,45 @@ int smhip_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, 
 int smhip_reduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask,
                       int *route, int *launches, int64_t *ori3);
 
+/* ------------------------------------------------------- cumulative scans */
+/* np.cumsum / np.cumprod / np.maximum.accumulate / np.minimum.accumulate along ONE axis:
+ *     out[..., r, ...] = fold over k <= r of a[..., k, ...]          inclusive, forward.  The contract:
+ *   kind   f32                                          f64         i32 / i64
+ *   SUM    running sum held in fp64, each output        fp64        wrapping in the type's width (= np.cumsum(x, axis,
+ *          rounded once to f32                                      dtype=T); bit-exact in any order)
+ *   PROD   running product held in fp64, each output    fp64        wrapping (= np.cumprod(x, axis, dtype=T))
+ *          rounded once
+ *   MAX    exact; once a NaN is met every later output  the same    exact
+ *   MIN    along the axis is NaN (as np.maximum.accumulate);
+ *          which zero a +-0 tie gives is not specified
+ * The scan is blocked: it combines partial folds of runs of consecutive elements.  So
+ *   - a float SUM or PROD is the value of SOME fixed parenthesisation of a[0] .. a[r]: the error of output r is at most
+ *     r * 2^-53 * sum_{k<=r} |a[k]| for SUM and r * 2^-53 relative for PROD, plus the final rounding for f32;
+ *   - a float PROD whose partial product over some run of consecutive elements overflows or underflows in fp64 may give
+ *     inf / 0 / NaN where a strictly sequential product would not.
+ * Deterministic: the bits depend only on the dtype, the kind, the shape and the layout -- a fixed partition of the work,
+ * carries combined in index order, no float atomics. */
+typedef enum smhip_scan_kind { SMHIP_SCAN_SUM = 0, SMHIP_SCAN_PROD = 1, SMHIP_SCAN_MAX = 2, SMHIP_SCAN_MIN = 3 } smhip_scan_kind;
+/* `a` is any view (strides in ELEMENTS, >= 0; rank 1 .. SMHIP_MAX_NDIM); `out` is dense row-major over `shape`.  out == a is
+ * allowed when `a` is dense (in place); any other overlap of the two is SMHIP_ERR_INVALID.  An extent of 0 is a no-op.
+ * Arguments are checked before any device is touched: kind, dtype (f32, f64, i32, i64), ndim, axis in [0, ndim), negative
+ * extents or strides, null pointers, the overlap.  Asynchronous, stream-ordered; recorded tiny operators are flushed first. */
+int smhip_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim,
+                    int axis, void *out);
+/* Host only, no device touched: the route smhip_scan_axis would take.  *route = a kernel id (SMHIP_SCAN_ROUTE_*) ORed with the
+ * flags below; *launches = the kernel launches of the whole call; ori3 = {O, R, I}, the extents before the axis, of the axis
+ * and after it (out[o, r, i] = scan_r a[o, r, i]); *chunk = the length of the chunks R is cut into (R itself when it is
+ * not).  Any output may be NULL.  The planner's test hook. */
+#define SMHIP_SCAN_ROUTE_NONE 0      /* an extent is 0: nothing to compute */
+#define SMHIP_SCAN_ROUTE_COPYONLY 1  /* R = 1: the dense copy of a (nothing when in place) */
+#define SMHIP_SCAN_ROUTE_ROW 2       /* I = 1: each row of R elements contiguous; DPP scan in the wave, wave totals through LDS */
+#define SMHIP_SCAN_ROUTE_COLUMN 3    /* I > 1: a lane owns 4 consecutive i; a 16 x 16 workgroup walks R in blocks of rows */
+#define SMHIP_SCAN_SPLIT 0x100       /* R cut into fixed chunks (the shape decides): launch 1 leaves each chunk's total, launch 2
+                                        starts each chunk from the fold, in index order, of the totals before it */
+#define SMHIP_SCAN_COPY 0x200        /* the operand is not dense row-major: copied dense first (one launch more) */
+int smhip_scan_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                    int *route, int *launches, int64_t *ori3, int64_t *chunk);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

@@ -38,6 +38,11 @@ REDUCE_KINDS = {"sum": REDUCE_SUM, "mean": REDUCE_MEAN, "max": REDUCE_MAX, "min"
 # smhip_reduce_plan's route word: a kernel id in the low byte, flags above it
 ROUTE_NONE, ROUTE_ROW, ROUTE_COLUMN, ROUTE_CHANNEL, ROUTE_FILL, ROUTE_GATHER = range(6)
 ROUTE_SPLIT, ROUTE_COPY, ROUTE_PASSES = 0x100, 0x200, 0x400
+SCAN_SUM, SCAN_PROD, SCAN_MAX, SCAN_MIN = range(4)  # smhip_scan_kind
+SCAN_KINDS = {"cumsum": SCAN_SUM, "cumprod": SCAN_PROD, "cummax": SCAN_MAX, "cummin": SCAN_MIN}
+# smhip_scan_plan's route word: a kernel id in the low byte, flags above it
+SCAN_ROUTE_NONE, SCAN_ROUTE_COPYONLY, SCAN_ROUTE_ROW, SCAN_ROUTE_COLUMN = range(4)
+SCAN_SPLIT, SCAN_COPY = 0x100, 0x200
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -556,6 +561,46 @@ class Smhip:
         self._ck(self.c.smhip_reduce_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)),
                                           C.c_uint32(sum(1 << d for d in axes)), C.byref(route), C.byref(launches), ori))
         return route.value, launches.value, tuple(int(x) for x in ori)
+
+    def scan(self, kind, a: DeviceArray, axis=None, out: DeviceArray | None = None):
+        """np.cumsum / np.cumprod / np.maximum.accumulate / np.minimum.accumulate of `a` (any view) along `axis` ("cumsum",
+        "cumprod", "cummax", "cummin" or the smhip_scan_kind value) -> a new dense DeviceArray of a's shape, or into `out`,
+        which must be a dense array of a's dtype and element count (its shape is not changed); `out` may be `a` itself when
+        `a` is dense (in place).  axis=None scans the elements in row-major order and gives shape (a.size,)."""
+        kind = SCAN_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if axis is None:
+            if not a.is_dense():  # the row-major order of a view: its dense copy
+                dense = self.empty(a.shape, a.dtype)
+                self.assign(dense, a)
+                a = dense
+            shape, strides, axis, result_shape = (a.size,), (1,), 0, (a.size,)
+        else:
+            (axis,) = self._axes(a.ndim, int(axis))
+            shape, strides, result_shape = a.shape, a.strides, a.shape
+        if out is None:
+            out = self.empty(result_shape, a.dtype)
+        elif out.dtype != a.dtype or out.size != a.size or not out.is_dense():
+            raise ValueError(f"scan: out must be a dense {a.dtype} array of {a.size} elements (shape {tuple(result_shape)}); "
+                             f"got {out.dtype} {out.shape} dense={out.is_dense()}")
+        self._ck(self.c.smhip_scan_axis(C.c_int(kind), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(shape), _i64(strides),
+                                        C.c_int(len(shape)), C.c_int(axis), C.c_void_p(out.ptr)))
+        return out
+
+    def scan_raw(self, kind, dtype, a_ptr, shape, strides, axis, out_ptr, ndim=None):
+        """smhip_scan_axis with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        return self.c.smhip_scan_axis(C.c_int(kind), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                      _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_int(axis), C.c_void_p(out_ptr))
+
+    def scan_plan(self, kind, dtype, shape, strides, axis):
+        """smhip_scan_plan (host only): (route word, launches, (O, R, I), chunk length) for a call on shape / strides (elements)."""
+        kind = SCAN_KINDS[kind] if isinstance(kind, str) else int(kind)
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        route, launches, ori, chunk = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), C.c_int64(0)
+        self._ck(self.c.smhip_scan_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)),
+                                        C.byref(route), C.byref(launches), ori, C.byref(chunk)))
+        return route.value, launches.value, tuple(int(x) for x in ori), chunk.value
 
     def sum(self, a: DeviceArray):
         out = C.c_double(0)

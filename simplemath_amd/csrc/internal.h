@@ -222,4 +222,11 @@ void reduce_axes_plan(int dtype, const int64_t *shape, const int64_t *strides, i
 int launch_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, void *out,
                        hipStream_t s);
 
+// scan_axis.hip: cumulative scans along an axis (smhip_scan_axis); the checks and the planner are host-only
+int scan_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis);
+void scan_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
+                    int64_t *chunk);
+int launch_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *out,
+                     hipStream_t s);
+
 }  // namespace smhip

@@ -34,6 +34,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "fold.hip.h"
 #include "internal.h"
 #include "ops.hip.h"
 #include "wave.hip.h"
@@ -43,44 +44,11 @@ namespace {
 
 using namespace dev;
 
-enum Kind { kSum = 0, kMax = 2, kMin = 3 };  // mean = kSum and a divisor at the last launch
 constexpr int kBlock = 256;
 constexpr int kChannelMax = 8;                 // CHANNEL route: at most this many kept columns
 constexpr int64_t kChannelMinR = 4 * kBlock;    // ... and at least one workgroup step of stream (256 * I vectors) per outer
                                                 // index: shorter blocks go to COLUMN, whose lanes pack several (o, c) tasks
 constexpr int64_t kTargetLanes = (int64_t)1 << 18;  // lanes a launch should have before R is split (256 CUs x 1024)
-
-template <typename T, int K> struct Acc { typedef T type; };
-template <> struct Acc<float, kSum> { typedef double type; };
-template <> struct Acc<double, kSum> { typedef double type; };
-template <> struct Acc<int32_t, kSum> { typedef uint64_t type; };  // wrapping: exact modulo 2^64, hence modulo 2^32
-template <> struct Acc<int64_t, kSum> { typedef uint64_t type; };
-
-template <typename A, int K> __device__ __forceinline__ A fold(A x, A y) {
-    if constexpr (K == kSum) return x + y;
-    else if constexpr (K == kMax) {
-        if constexpr (std::is_floating_point<A>::value) return (x > y || x != x) ? x : y;  // NaN in either propagates
-        else return x > y ? x : y;
-    } else {
-        if constexpr (std::is_floating_point<A>::value) return (x < y || x != x) ? x : y;
-        else return x < y ? x : y;
-    }
-}
-template <typename A, int K> __device__ __forceinline__ A identity() {
-    if constexpr (K == kSum) return A(0);
-    else if constexpr (K == kMax) return std::is_floating_point<A>::value ? -std::numeric_limits<A>::infinity() : std::numeric_limits<A>::lowest();
-    else return std::is_floating_point<A>::value ? std::numeric_limits<A>::infinity() : std::numeric_limits<A>::max();
-}
-template <typename TI, typename A> __device__ __forceinline__ A widen(TI x) {
-    if constexpr (std::is_integral<TI>::value && std::is_unsigned<A>::value) return (A)(int64_t)x;  // sign-extended, then wrapping
-    else return (A)x;
-}
-// The accumulator to the launch's output type; `divisor` > 0: the mean's one division (fp64), then one rounding.
-template <typename TO, typename A> __device__ __forceinline__ TO finish(A acc, double divisor) {
-    if constexpr (std::is_integral<TO>::value) return (TO)(int64_t)acc;  // the wrapped residue
-    else if constexpr (std::is_same<A, double>::value) return divisor > 0.0 ? (TO)(acc / divisor) : (TO)acc;
-    else return (TO)acc;
-}
 
 // Where a launch's results go: out[o*oso + i*osi + c*ocs] (c = the chunk of R; 0 when R is not split).
 struct OutMap { int64_t oso, osi, ocs; };
@@ -187,7 +155,6 @@ __global__ __launch_bounds__(kBlock) void row_long_kernel(const TI *__restrict__
 // ---- COLUMN: a lane owns kept columns i0 .. i0 + 3 of outer index o and walks rows [c*CL, c*CL + CL) of R.  Lanes are
 // numbered (o, c, quad) with the quad fastest and packed without gaps: with few columns (I = 9 .. 1023, or I <= 8 over short
 // R) one wave still covers several (o, c) tasks instead of leaving most of a workgroup idle.  Grid-stride over the lanes.
-template <typename T> struct Quad { typedef T type __attribute__((ext_vector_type(4), aligned(sizeof(T)))); };
 template <typename TI, typename TO, int K>
 __global__ __launch_bounds__(kBlock) void column_kernel(const TI *__restrict__ a, int64_t O, int64_t so, int64_t R, int64_t sr, int64_t I,
                                                         int64_t CL, int64_t C, TO *__restrict__ out, OutMap om, double divisor, int nt) {

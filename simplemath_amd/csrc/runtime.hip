@@ -108,11 +108,13 @@ struct Arena {
     std::vector<Extent> free;  // sorted by offset, coalesced
 };
 struct Block { size_t cls; int device; Arena *arena; size_t off; hipStream_t stream; std::thread::id owner; };
+// Declared BEFORE the tables whose tags own recorded events: at exit those tables are destroyed first and hand their events
+// back (Recorded::~Recorded), so the pool they go to must still be alive then.
+std::mutex g_event_mutex;
+std::vector<hipEvent_t> g_event_pool[kMaxDevices];  // timing-disabled events, recycled
 std::unordered_map<void *, Block> g_live;                                      // handed out
 std::map<std::pair<int, size_t>, std::vector<std::pair<void *, Tag>>> g_free;  // small blocks, cached
 std::vector<Arena *> g_arenas;
-std::mutex g_event_mutex;
-std::vector<hipEvent_t> g_event_pool[kMaxDevices];  // timing-disabled events, recycled
 uint64_t g_record_seq = 0;
 size_t g_bytes_live = 0, g_bytes_cached = 0;
 
@@ -1455,6 +1457,33 @@ int smhip_reduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *
                       int64_t *ori3) {
     if (int rc = reduce_axes_check("reduce_plan", kind, dtype, shape, strides, ndim, axes_mask)) return rc;
     reduce_axes_plan(dtype, shape, strides, ndim, axes_mask, route, launches, ori3);
+    return SMHIP_OK;
+}
+
+int smhip_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *out) {
+    if (int rc = scan_axis_check("scan_axis", kind, dtype, shape, strides, ndim, axis)) return rc;
+    int64_t n = 1;
+    bool dense = true;
+    for (int d = ndim - 1; d >= 0; --d) {
+        if (shape[d] != 1 && strides[d] != n) dense = false;
+        n *= shape[d];
+    }
+    if (n == 0) return SMHIP_OK;
+    if (!a || !out) return fail(SMHIP_ERR_INVALID, "scan_axis: null buffer");
+    if (!(out == a && dense)) {  // in place is the one overlap a scan can take: a lane stores only what it has loaded itself
+        const size_t esz = dtype_size(dtype);
+        const char *a0 = static_cast<const char *>(a), *o0 = static_cast<const char *>(out);
+        if (a0 < o0 + (size_t)n * esz && o0 < a0 + span_bytes(shape, strides, ndim, esz))
+            return fail(SMHIP_ERR_INVALID, "scan_axis: the result overlaps the operand (only out == a with a dense operand is allowed)");
+    }
+    SMHIP_ACQUIRE(s);  // undeclared spans (a pooled copy, the chunks' totals): ordered behind everything, recorded tiny operators flushed first
+    return launch_scan_axis(kind, dtype, a, shape, strides, ndim, axis, out, s);
+}
+
+int smhip_scan_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches,
+                    int64_t *ori3, int64_t *chunk) {
+    if (int rc = scan_axis_check("scan_plan", kind, dtype, shape, strides, ndim, axis)) return rc;
+    scan_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
     return SMHIP_OK;
 }
 

@@ -1,5 +1,5 @@
-// wave.hip.h -- in-wave folds through DPP moves, shared by reduce.hip (whole-array reductions) and reduce_axis.hip (axis
-// reductions).
+// wave.hip.h -- in-wave folds and scans through DPP moves, shared by reduce.hip (whole-array reductions), reduce_axis.hip (axis
+// reductions) and scan_axis.hip (cumulative scans).
 #pragma once
 
 #include <stdint.h>
@@ -66,6 +66,30 @@ template <typename A, typename F> __device__ __forceinline__ A segment_fold(A v,
     if (g >= 64) v = f(v, dpp_move_or<0x143, 0xc>(v, id));
     return v;
 }
+
+// The same moves as an inclusive SCAN (scan_axis.hip): after it lane i holds f over lanes s*g .. i of its segment of g lanes
+// (g = 1, 2, 4, ..., 64, wave-uniform; `lane` = the lane's number in the wave), earlier lanes on the left of f.  A step whose
+// source lies in the segment before is skipped, so every lane's value is valid, not only the segment's last.  Every value
+// that meets another in f covers the lanes just before it: a fold of runs of CONSECUTIVE lanes, in a fixed order.  All 64
+// lanes must be active.
+template <typename A, typename F> __device__ __forceinline__ A segment_scan(A v, int g, int lane, A id, F f) {
+    const int sl = lane & ((g < 16 ? g : 16) - 1);  // the lane's place in its segment, or in its row of 16
+    A m;
+    if (g >= 2) { m = dpp_move_or<0x111, 0xf>(v, id); v = sl >= 1 ? f(m, v) : v; }    // row_shr:1
+    if (g >= 4) { m = dpp_move_or<0x112, 0xf>(v, id); v = sl >= 2 ? f(m, v) : v; }    // row_shr:2
+    if (g >= 8) { m = dpp_move_or<0x114, 0xf>(v, id); v = sl >= 4 ? f(m, v) : v; }    // row_shr:4
+    if (g >= 16) { m = dpp_move_or<0x118, 0xf>(v, id); v = sl >= 8 ? f(m, v) : v; }   // row_shr:8
+    if (g >= 32) { m = dpp_move_or<0x142, 0xa>(v, id); v = (lane & 16) ? f(m, v) : v; }  // row_bcast:15 into rows 1 and 3
+    if (g >= 64) { m = dpp_move_or<0x143, 0xc>(v, id); v = (lane & 32) ? f(m, v) : v; }  // row_bcast:31 into rows 2 and 3
+    return v;
+}
+// The value of the lane before (wave_shr:1), `id` in the first lane of each segment of g lanes: the scan of it is the
+// EXCLUSIVE scan of v.  All 64 lanes must be active.
+template <typename A> __device__ __forceinline__ A segment_prev(A v, int g, int lane, A id) {
+    const A p = dpp_move_or<0x138, 0xf>(v, id);
+    return (lane & (g - 1)) == 0 ? id : p;
+}
+template <typename A, typename F> __device__ __forceinline__ A wave_scan(A v, int lane, A id, F f) { return segment_scan(v, 64, lane, id, f); }
 
 }  // namespace dev
 }  // namespace smhip
