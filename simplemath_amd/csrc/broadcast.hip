@@ -81,12 +81,6 @@ template <typename T, typename Op, bool VEC, int MA, int MB, int QB>
 __global__ __launch_bounds__(256) void tile_kernel(const T *__restrict__ a, const T *__restrict__ b, T *__restrict__ out, TileParams p) {
     tile_body<T, Op, VEC, MA, MB, QB>(a, b, out, p);
 }
-#if SMHIP_TILE_SHIFT_FORM
-template <typename T, typename Op, int MA, int MB, int QB>
-__global__ __launch_bounds__(256) void tile_shift_kernel(const T *__restrict__ a, const T *__restrict__ b, T *__restrict__ out, TileParams p) {
-    tile_shift_body<T, Op, MA, MB, QB>(a, b, out, p);
-}
-#endif
 
 // ---------------------------------------------------------------------------- choosing a kernel
 // plan_launch() turns a normalised problem into a Launch: which body, which compile-time variant of it, the grid and the
@@ -312,30 +306,18 @@ int plan_launch(const Plan &pl, int esz, bool heavy, Launch *L) {
                 L->kind = Launch::kTile;
                 L->vec = vec;
                 L->qb = qb;
-                static const int forced_order = [] { const char *e = getenv("SMHIP_TILE_ORDER"); return e && *e ? atoi(e) : -1; }();
+                // SMHIP_TILE_ORDER = 0 / 1 forces the walk (tools/tile_variants.sh); any other value counts as unset
+                static const int forced_order = [] { const char *e = getenv("SMHIP_TILE_ORDER"); const int v = e && *e ? atoi(e) : -1; return v == 0 || v == 1 ? v : -1; }();
                 // output rows that do not start on 128-byte lines (an inner extent like 8190): neighbouring patches share the
                 // lines at their seams, and the row-major walk runs them back to back (8190 x 8190: 61 -> 77 %, cold 48 -> 61 %)
                 const bool ragged_rows = ((size_t)inner * (size_t)esz) % 128 != 0;
-                // (order 2 -- the row-major walk in eight runs, one per XCD, so that the patches on either side of a seam meet in one
-                // L2 -- was measured for ragged rows and NOT adopted: 8191^2 75.7 -> 77.7 %, but 12287^2 60.3 -> 56.3 % and 16383^2
-                // 60 -> 57.6 %; SMHIP_TILE_ORDER=2 selects it; profiles/r04_pmc_tile_odd.txt)
-                t.order = forced_order >= 0 ? (uint32_t)forced_order : (qb == kTileQBytesWide || ragged_rows) ? 0 : 1;  // SMHIP_TILE_ORDER: for tools/tile_variants.sh
+                // (The row-major walk in eight runs, one per XCD, so that the patches on either side of a seam meet in one L2, was
+                // measured for ragged rows and NOT adopted: 8191^2 75.7 -> 77.7 %, but 12287^2 60.3 -> 56.3 % and 16383^2
+                // 60 -> 57.6 %; profiles/r04_pmc_tile_odd.txt.  Its code is retired: DESIGN.md section 8.)
+                t.order = forced_order >= 0 ? (uint32_t)forced_order : (qb == kTileQBytesWide || ragged_rows) ? 0 : 1;
                 L->ma = L->vec ? t.mode_a : 0;
                 L->mb = L->vec ? t.mode_b : 0;
                 L->grid = (unsigned)blocks;
-                if (t.order == 3) {  // blocks of BP x BQ patches dealt to the XCDs in turn (SMHIP_TILE_BLOCK = BP * 16 + BQ in hex digits: 24 = 2 x 4)
-                    static const int blk = [] { const char *e = getenv("SMHIP_TILE_BLOCK"); return e && *e ? (int)strtol(e, nullptr, 16) : 0x24; }();
-                    const uint32_t BP = (uint32_t)(blk >> 4) & 15u ? (uint32_t)(blk >> 4) & 15u : 1u, BQ = (uint32_t)blk & 15u ? (uint32_t)blk & 15u : 1u;
-                    const size_t rows = slices * t.tiles_p, nblocks = ((rows + BP - 1) / BP) * ((t.tiles_q + BQ - 1) / BQ);
-                    const size_t g = (nblocks + 7) / 8 * 8 * BP * BQ;
-                    if (g < 0x7fffffffull) { t.total = BP | (BQ << 8); L->grid = (unsigned)g; }
-                    else t.order = 0;
-                }
-                if (t.order == 2) {  // eight runs of the row-major walk, one per XCD (bcast_kernels.hip.h: tile_body)
-                    t.total = (uint32_t)blocks;
-                    L->grid = (unsigned)((blocks + 7) / 8 * 8);
-                    if (blocks + 8 >= 0x7fffffffull) { t.order = 0; L->grid = (unsigned)blocks; }
-                }
                 return SMHIP_OK;
             }
         }
@@ -463,32 +445,6 @@ int launch_aot(const Launch &L, const void *a_, const void *b_, void *out_, hipS
         case Launch::kTile:
             if (!L.vec) return fail(SMHIP_ERR_INVALID, "tile kernel: the plan always asks for the 16-byte form");  // (the one-element-per-slot form is no longer built: the 16-byte form takes every extent)
             else {
-#if SMHIP_TILE_SHIFT_FORM
-                // Output rows off the 128-byte lines, past the Infinity Cache: patches whose rows are cut at LINES, not columns
-                // (bcast_kernels.hip.h: tile_shift_body) -- measured and not adopted, see there; built only with -DSMHIP_TILE_SHIFT_FORM=1.
-                {
-                    const TileParams &t = L.p.tile;
-                    static const int shift_mode = [] { const char *e = getenv("SMHIP_TILE_SHIFT"); return e && *e ? atoi(e) : 0; }();  // 0: off (default), 1: rows off the lines, 2: also for rows ON the lines (the form's own cost)
-                    const bool shift_on = shift_mode != 0;
-                    constexpr uint32_t TQ = kTileQBytesWide / sizeof(T), G = kTileShiftBytes / sizeof(T);
-                    const bool both = L.ma == 1 && L.mb == 1;
-                    const int64_t direct_q = L.ma == 1 ? t.b_q : t.a_q;
-                    if (shift_on && L.qb == kTileQBytesWide && t.order == 0 && !t.in_place && t.np >= 4u * kTileP && t.nq >= 2u * TQ &&
-                        (((size_t)t.nq * sizeof(T)) % kTileShiftBytes != 0 || shift_mode == 2) && (both || direct_q == 1 || direct_q == 0)) {
-                        TileParams ts = t;
-                        ts.tiles_q = (t.nq + G - 1 + TQ - 1) / TQ;
-                        const size_t blocks = (size_t)L.grid / ((size_t)t.tiles_p * t.tiles_q) * ts.tiles_p * ts.tiles_q;
-                        if (blocks < 0x7fffffffull) {
-                            const dim3 sgrid((unsigned)blocks);
-                            if (both) hipLaunchKernelGGL((tile_shift_kernel<T, Op, 1, 1, kTileQBytesWide>), sgrid, block, 0, s, a, b, out, ts);
-                            else if (L.ma == 1) hipLaunchKernelGGL((tile_shift_kernel<T, Op, 1, 0, kTileQBytesWide>), sgrid, block, 0, s, a, b, out, ts);
-                            else hipLaunchKernelGGL((tile_shift_kernel<T, Op, 0, 1, kTileQBytesWide>), sgrid, block, 0, s, a, b, out, ts);
-                            SMHIP_LAUNCH_CHECK("tile_shift_kernel");
-                            return SMHIP_OK;
-                        }
-                    }
-                }
-#endif
                 auto go = [&](auto qb_tag) {
                     constexpr int QB = decltype(qb_tag)::value;
                     if (L.ma == 1 && L.mb == 1) hipLaunchKernelGGL((tile_kernel<T, Op, true, 1, 1, QB>), grid, block, 0, s, a, b, out, L.p.tile);
@@ -1014,8 +970,7 @@ __global__ __launch_bounds__(256) void planes_kernel(const T *__restrict__ t, co
 
 // Is the normalised problem a dense batch of small planes with one operand read transposed?
 inline bool plan_planes(const Plan &pl, int esz, PlanesParams *pp, bool *t_is_a) {
-    static const bool off = [] { const char *e = getenv("SMHIP_PLANES_KERNEL"); return e && *e && atoi(e) == 0; }();  // tools: SMHIP_PLANES_KERNEL=0
-    if (off || pl.ndim != 3) return false;
+    if (pl.ndim != 3) return false;
     const int64_t B = pl.shape[0], P = pl.shape[1], Q = pl.shape[2], PQ = P * Q;
     const int W = 16 / esz, cmax = 32768 / esz;
     if (P < 2 || Q < 2 || PQ > cmax || B < 64) return false;
@@ -1066,8 +1021,7 @@ inline bool plan_record(const Plan &pl, int esz, RecordParams *rp, bool *small_p
     *t_is_a = ta;
     RecordParams r{};
     r.o_scalar = scalar(so) ? 1 : 0;
-    static const int64_t max_p = [] { const char *e = getenv("SMHIP_RECORD_MAX_P"); return e && *e ? (int64_t)atoi(e) : (int64_t)128; }();
-    static const int64_t max_q = [] { const char *e = getenv("SMHIP_RECORD_MAX_Q"); return e && *e ? (int64_t)atoi(e) : (int64_t)128; }();
+    constexpr int64_t max_p = 128, max_q = 128;  // the record kernel's limits on the small extent
     if (P <= max_p && Q >= 4096 && st[1] == P) {            // few long rows out of dense records: AoS -> SoA
         *small_p = true;
         r.k = (uint32_t)P; r.n = (uint64_t)Q;
@@ -1155,11 +1109,7 @@ __global__ __launch_bounds__(256) void strided_copy_kernel(const T *__restrict__
     const uint32_t e0 = col * W;
     if constexpr (VEC) {
         if (e0 + W <= p.inner) {
-#ifdef SMHIP_COPY_PLAIN_STORES
-            *reinterpret_cast<V *>(dst + offD + e0) = load_stream_if(T, reinterpret_cast<const V *>(src + offS + e0), p.nt);
-#else
             store_stream_if(T, reinterpret_cast<V *>(dst + offD + e0), load_stream_if(T, reinterpret_cast<const V *>(src + offS + e0), p.nt), p.nt);
-#endif
         } else {
             for (uint32_t e = e0; e < p.inner; ++e) dst[offD + e] = src[offS + e];
         }
@@ -1528,7 +1478,7 @@ int launch_plan(int op, int dtype, const void *a, const void *b, void *out, cons
         }
     }
     // short rows of a view against a dense partner or another view (both stepping by one along the row)
-    static const int64_t pitched_max = [] { const char *e = getenv("SMHIP_PITCHED_ROWS_MAX"); return e && *e ? (int64_t)atoi(e) : (int64_t)4096; }();
+    constexpr int64_t pitched_max = 4096;  // rows of a view shorter than this take the pitched-rows kernel
     auto rowwise = [&](const int64_t *st) { return st[1] == 1 && st[0] >= pl.shape[1]; };        // steps by one along the row
     auto onevalue = [&](const int64_t *st) { return st[0] == 0 && st[1] == 0; };
     auto pitched = [&](const int64_t *st) { return rowwise(st) && st[0] != pl.shape[1]; };        // ... and is a view

@@ -222,11 +222,12 @@ __device__ __forceinline__ typename VecTraits<T>::full_t chain_eval(const ChainA
 // One tile of blockDim.x * U vectors per workgroup, no loop over the data.  Full tiles are guard-free: all U x ND streaming
 // loads of a lane go out in one block (inside one arm of the read-policy branch), then the small operands' cached loads,
 // then the stages and the stores.  The last, partial tile and the n % W tail elements take the guarded path.
-template <typename T, int ND, int NR, int NS, int U, bool UNARY>
+template <typename T, int ND, int NR, int NS, bool UNARY>
 __global__ __launch_bounds__(1024) void chain_kernel(ChainArgs<T> A, T *__restrict__ out, size_t n_vec, int tail, int pol) {
     typedef typename VecTraits<T>::vec_t V;
     typedef typename VecTraits<T>::full_t F;
     constexpr int W = VecTraits<T>::width;
+    constexpr int U = 1;  // vectors per lane (two were measured and lost: launch_variant)
     const size_t tile = (size_t)blockDim.x * U;
     const size_t base = (size_t)blockIdx.x * tile + threadIdx.x;
     if (((size_t)blockIdx.x + 1) * tile <= n_vec) {
@@ -417,13 +418,13 @@ LeafKind classify(const Problem &pb, const int64_t *strides, uint64_t *P, uint64
     return kComplex;
 }
 
-template <typename T, int U, bool UNARY>
-int launch_variant_u(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t n_vec, int tail, int pol, int block, hipStream_t s) {
-    const size_t tiles = n_vec / ((size_t)block * U) + 1;  // the last workgroup: partial tile + tail elements (maybe empty)
+template <typename T, bool UNARY>
+int launch_variant_block(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t n_vec, int tail, int pol, int block, hipStream_t s) {
+    const size_t tiles = n_vec / (size_t)block + 1;  // the last workgroup: partial tile + tail elements (maybe empty)
     if (tiles > 0x7fffffffu) return fail(SMHIP_ERR_UNSUPPORTED, "chain: array too large for one launch");
     const dim3 grid((unsigned)tiles), blk(block);
 #define SMHIP_CHAIN_CASE(ND, NR, NS) \
-    case (ND) * 9 + (NR) * 3 + (NS): hipLaunchKernelGGL((chain_kernel<T, ND, NR, NS, U, UNARY>), grid, blk, 0, s, A, out, n_vec, tail, pol); break;
+    case (ND) * 9 + (NR) * 3 + (NS): hipLaunchKernelGGL((chain_kernel<T, ND, NR, NS, UNARY>), grid, blk, 0, s, A, out, n_vec, tail, pol); break;
 #define SMHIP_CHAIN_SMALL(ND) \
     SMHIP_CHAIN_CASE(ND, 0, 1) SMHIP_CHAIN_CASE(ND, 0, 2) SMHIP_CHAIN_CASE(ND, 1, 0) SMHIP_CHAIN_CASE(ND, 1, 1) SMHIP_CHAIN_CASE(ND, 1, 2) \
     SMHIP_CHAIN_CASE(ND, 2, 0) SMHIP_CHAIN_CASE(ND, 2, 1) SMHIP_CHAIN_CASE(ND, 2, 2)
@@ -443,8 +444,6 @@ int launch_variant_u(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size
 
 template <typename T>
 int launch_variant(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t n_vec, int tail, int pol, bool unary, hipStream_t s) {
-    static const int forced_block = [] { const char *e = getenv("SMHIP_CHAIN_BLOCK"); return e && *e ? atoi(e) : 0; }();  // experiments
-    static const int forced_u = [] { const char *e = getenv("SMHIP_CHAIN_U"); return e && *e ? atoi(e) : 0; }();
     // workgroups of 256, one vector per lane: (A * row + B) * 0.5 at 4096 x 4096 29.9 us (84 % of peak on its 12 B/elem) against
     // 31.1 with 1024 threads and 29.6 / 32.7 with two vectors per lane; at 8192 x 8192 121.5 against 137.8 / 122.9 / 140.3 us
     // (tools/chain_fused_rates.py, profiles/r04_chain_shapes.txt)
@@ -452,13 +451,9 @@ int launch_variant(int nd, int nr, int ns, const ChainArgs<T> &A, T *out, size_t
     // profiles/r04_chain_block.txt: (A * row + B) * 0.5 at 4096^2 82.3 -> 84.2 %, at 8192^2 80.0 -> 83.6, on rotating operands
     // 77.1 -> 78.8; (A + B) * 0.5 rotating 75.9 -> 78.3 -- but splat forms on rotating operands 80 -> 75 and everything at
     // 16384 x 8192 one to five points WORSE)
-    const bool clamp_ok = forced_block >= 64 && forced_block <= 1024 && forced_block % 64 == 0;
-    const int block = clamp_ok ? forced_block : (ns == 0 && n_vec <= ((size_t)1 << 24) ? 512 : 256);
-    (void)nd;
-    const int u = forced_u ? forced_u : 1;
-    if (unary) return launch_variant_u<T, 1, true>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);  // (one vector per lane only)
-    if (u == 2) return launch_variant_u<T, 2, false>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
-    return launch_variant_u<T, 1, false>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
+    const int block = ns == 0 && n_vec <= ((size_t)1 << 24) ? 512 : 256;
+    if (unary) return launch_variant_block<T, true>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
+    return launch_variant_block<T, false>(nd, nr, ns, A, out, n_vec, tail, pol, block, s);
 }
 
 // A few items in place: planning a chain allocates nothing (a chain call on a 4 MB array is host-bound: every 100 ns of
@@ -563,8 +558,7 @@ int run_segment(const Problem &pb, const Segment &sg, void *out_, hipStream_t s)
             A.spl_q0[k] = (uint32_t)((at / r) % spls[k]->C);
             // a wave's 64 vectors are consecutive and start at a multiple of 64: with R a whole number of those, and the piece
             // starting on one, every lane of a wave wants the SAME element -- the index is scalar arithmetic and one scalar load
-            static const bool uniform_ok = [] { const char *e = getenv("SMHIP_CHAIN_UNIFORM_SPLAT"); return !(e && *e && atoi(e) == 0); }();
-            if (!elem && uniform_ok && r % 64 == 0 && A.spl_r0[k] % 64 == 0) A.spl_elem[k] = 2;
+            if (!elem && r % 64 == 0 && A.spl_r0[k] % 64 == 0) A.spl_elem[k] = 2;
         }
         if (int rc = launch_variant<T>(nd, nr, ns, A, out + v0 * W, nv, last ? tail : 0, pol, unary, s)) return rc;
         if (last) break;

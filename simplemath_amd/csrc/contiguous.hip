@@ -116,7 +116,7 @@ __global__ __launch_bounds__(BLOCK) void devscalar_vec_kernel(const T *__restric
 #ifndef SMHIP_FLAT_TILE_THREADS
 #define SMHIP_FLAT_TILE_THREADS 256
 #endif
-constexpr int kTileBlock = SMHIP_FLAT_TILE_THREADS;  // (512: tools/build_variant.sh; measured for config 3's cold leg on two queues)
+constexpr int kTileBlock = SMHIP_FLAT_TILE_THREADS;  // (512: tools/build_variant.sh ft512 -DSMHIP_FLAT_TILE_THREADS=512; measured for config 3's cold leg on two queues)
 // KEEP_STORES: the write side's policy (ops.hip.h: store_stream_if) as a template parameter -- as a run-time branch in
 // front of each store it cut the arithmetic of the tile's vectors apart (config 4: 73.2 -> 79.0 us).
 // KIND 0: a op b, 1: a op s, 2: s op a (the heavy Ops only); 3 / 4: a dense (rows x cols) against ONE ROW / ONE COLUMN of
@@ -124,11 +124,9 @@ constexpr int kTileBlock = SMHIP_FLAT_TILE_THREADS;  // (512: tools/build_varian
 // wants the same few KiB), resp. the single element b[i / cv].  Through the row kernel this shape paid ~35 vector
 // instructions per wave of index arithmetic on top of pow's 257 and staged the tables before its loads: 23.9 us at
 // 4096 x 4096 against 20.2 us here (profiles/r02_pow_shapes.txt; 21.1-21.8 us under the profiler, r02_pmc_sq_pow_shapes.txt).
-// BLOCK: 256 threads, except for the bank-private double pow (ops.hip.h: PowBanked), whose 80 KiB of tables want 1024.
-template <typename T, typename Op, int KIND, int U, bool KEEP_STORES, int BLOCK = kTileBlock>
-__global__ __launch_bounds__(BLOCK) void flat_tile_kernel(const T *__restrict__ a, const T *__restrict__ b, T s,
-                                                           T *__restrict__ out, size_t n_vec, int tail, int nt, FastDiv cv) {
-    constexpr int kTileBlock = BLOCK;  // shadows the file-scope default inside this kernel
+template <typename T, typename Op, int KIND, int U, bool KEEP_STORES>
+__global__ __launch_bounds__(kTileBlock) void flat_tile_kernel(const T *__restrict__ a, const T *__restrict__ b, T s,
+                                                                T *__restrict__ out, size_t n_vec, int tail, int nt, FastDiv cv) {
     typedef typename VecTraits<T>::vec_t V;
     constexpr int W = VecTraits<T>::width;
     OpCtx<Op> ctx;
@@ -234,77 +232,6 @@ __global__ __launch_bounds__(BLOCK) void flat_tile_kernel(const T *__restrict__ 
     }
 }
 
-// Measured and NOT adopted (round 3): -DSMHIP_POW64_BANKED=1 builds it for experiments.  N = 2^26, random
-// bases, scalar exponent: round 2's kernel 197.5-198.2 us (68 %; 172 us when every lane reads the same entry); bank-private
-// replicas as a one-shot launch 245.9 us (LDS bank conflicts 43 -> 12.7 % of the LDS-active cycles, but 80 KiB staged per
-// tile); persistent 213.7 us with two vectors per lane, 210.1 with three -- and 207 us even when every lane reads the same
-// entry: what the 1024-thread persistent form costs exceeds what the conflicts cost (profiles/r03_pow64_rate.txt).
-#ifndef SMHIP_POW64_BANKED
-#define SMHIP_POW64_BANKED 0
-#endif
-#ifndef SMHIP_POW64_BANKED_U
-#define SMHIP_POW64_BANKED_U 2
-#endif
-#if SMHIP_POW64_BANKED
-// double pow with bank-private tables (ops.hip.h: PowBanked), PERSISTENT: two 1024-thread workgroups per CU stage the 80 KiB
-// of replicas once and walk the tiles grid-stride.  As a one-shot launch (one tile per workgroup) the staging alone moved
-// 874 MB through the L2 for a 1 GiB array and the kernel LOST to round 2's (245.9 against 197.5 us, N = 2^26,
-// profiles/r03_pow64_rate.txt); arithmetic-bound as this Op is, eight resident waves per SIMD cover each other's loads
-// without a software pipeline.  KIND 0: a op b, 1: a op s, 2: s op a.
-template <int KIND, int U, bool KEEP_STORES>
-__global__ __launch_bounds__(1024, 8) void pow64_banked_kernel(const double *__restrict__ a, const double *__restrict__ b, double s,
-                                                                double *__restrict__ out, size_t n_vec, int tail, int nt) {
-    typedef double T;
-    typedef VecTraits<T>::vec_t V;
-    constexpr int W = VecTraits<T>::width, BLOCK = 1024;
-    OpCtx<PowBanked> ctx;
-    ctx.init();
-    const V *av = reinterpret_cast<const V *>(a), *bv = reinterpret_cast<const V *>(b);
-    V *ov = reinterpret_cast<V *>(out);
-    auto eval = [&](const V &xa, const V &xb) {
-        if constexpr (KIND == 0) return apply_vec<PowBanked, T>(ctx, xa, xb);
-        else return apply_vec_scalar<PowBanked, T, KIND == 2>(ctx, xa, s);
-    };
-    constexpr size_t kTile = (size_t)BLOCK * U;
-    const size_t full_tiles = n_vec / kTile;
-    for (size_t t = blockIdx.x; t < full_tiles; t += gridDim.x) {  // every wave's trip count is finite: t only grows
-        const size_t base = t * kTile + threadIdx.x;
-        V va[U], vb[U];
-        if (nt & kLoadNt) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                va[u] = load_stream_as(T, av + base + (size_t)u * BLOCK, true);
-                if constexpr (KIND == 0) vb[u] = load_stream_as(T, bv + base + (size_t)u * BLOCK, true);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                va[u] = load_stream_as(T, av + base + (size_t)u * BLOCK, false);
-                if constexpr (KIND == 0) vb[u] = load_stream_as(T, bv + base + (size_t)u * BLOCK, false);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) store_stream_as(T, ov + base + (size_t)u * BLOCK, eval(va[u], KIND == 0 ? vb[u] : va[u]), !KEEP_STORES);
-    }
-    if (blockIdx.x == full_tiles % gridDim.x) {  // the partial tile and the n % W tail: the workgroup whose turn it would be
-        for (size_t i = full_tiles * kTile + threadIdx.x; i < n_vec; i += BLOCK) {
-            const V va = load_stream(av + i);
-            V vb = va;
-            if constexpr (KIND == 0) vb = load_stream(bv + i);
-            store_stream(ov + i, eval(va, vb));
-        }
-        if (threadIdx.x == 0) {
-            for (int k = 0; k < tail; ++k) {
-                const T x = a[n_vec * W + k];
-                const T y = KIND == 0 ? b[n_vec * W + k] : s;
-                out[n_vec * W + k] = KIND == 2 ? PowBanked::apply(y, x) : PowBanked::apply(x, y);
-            }
-        }
-    }
-}
-
-#endif  // SMHIP_POW64_BANKED
-
 template <typename Op> struct IsHeavy : std::false_type {};
 // float / double pow only: integer pow is a short square-and-multiply loop, and the plain launch beats the pipelined one on
 // it for every exponent distribution tried (tools/ipow_exp.py: 80 % vs 64 % of peak for exponents < 32, 42 % vs 40 % for
@@ -348,9 +275,6 @@ inline bool m2_is_slow_chain(double s) {
 template <typename T, typename Op, int KIND>
 void launch_heavy(const T *pa, const T *pb, T value, T *po, size_t n_vec, int tail, hipStream_t s);
 
-#if SMHIP_POW64_BANKED
-constexpr int kBankedBlock = 1024;
-#endif
 template <typename T, typename Op, int KIND>
 void launch_heavy_piece(const T *pa, const T *pb, T value, T *po, size_t n_vec, int tail, int nt, hipStream_t s);
 
@@ -370,18 +294,6 @@ void launch_heavy(const T *pa, const T *pb, T value, T *po, size_t n_vec, int ta
 
 template <typename T, typename Op, int KIND>
 void launch_heavy_piece(const T *pa, const T *pb, T value, T *po, size_t n_vec, int tail, int nt, hipStream_t s) {
-#if SMHIP_POW64_BANKED
-    if constexpr (std::is_same<Op, PowOp<double>>::value) {
-        // double pow reads its tables from bank-private replicas: no lookup of a wave can collide with another (ops.hip.h: PowBanked)
-        constexpr int U = SMHIP_POW64_BANKED_U;
-        const size_t tiles = n_vec / ((size_t)kBankedBlock * U) + 1;
-        const size_t resident = (size_t)compute_units() * 2;  // two 1024-thread workgroups per CU: 80 KiB of LDS and 64 VGPRs each
-        const unsigned grid = (unsigned)(tiles < resident ? tiles : resident);
-        if (nt & kStoreKeep) hipLaunchKernelGGL((pow64_banked_kernel<KIND, U, true>), dim3(grid), dim3(kBankedBlock), 0, s, pa, pb, value, po, n_vec, tail, nt);
-        else hipLaunchKernelGGL((pow64_banked_kernel<KIND, U, false>), dim3(grid), dim3(kBankedBlock), 0, s, pa, pb, value, po, n_vec, tail, nt);
-        return;
-    }
-#endif
     // the lightest table form is served best by two vectors per lane (same box, tools/pow64_rate.py with -DSMHIP_HEAVY_F64_TILE_SCALAR=2 / 3 / 4:
     // LEVEL 2 78.0-78.3 / 77.2-77.7 / 76.5-77.0 %; LEVEL 1 75.1-76.7 / 77.7-78.3 / 77.1-77.5 %; profiles/r04_pow64_rate.txt)
     constexpr int U = std::is_same<Op, PowScalar64<2>>::value ? 2 : HeavyTile<T, KIND>::value;
@@ -427,8 +339,7 @@ int run_heavy_rows(const void *a, const void *b, void *out, size_t rows, size_t 
     // twice its size 44.2 -> 42.5 us (75.9 -> 79.0 %) -- while replayed and chained operands keep two (19.27 against 19.41 us;
     // tools/cold_rates.py, profiles/r03_rows_u.txt): twice the workgroups retire, and free their slots, half a tile earlier.
     const bool cold = (nt & kLoadNt) != 0;  // cold by the residency rule, or simply larger than the cache
-    static const int cold_u = [] { const char *e = getenv("SMHIP_FLAT_ROWS_COLD_U"); return e && *e ? atoi(e) : 1; }();  // experiments
-    if (!IsHeavy<Op>::value && U > 1 && cold && cold_u == 1) launch_rows<T, Op, 1>(pa, pb, po, n_vec, b_is_row, nt, cv, s);
+    if (!IsHeavy<Op>::value && U > 1 && cold) launch_rows<T, Op, 1>(pa, pb, po, n_vec, b_is_row, nt, cv, s);
     else launch_rows<T, Op, U>(pa, pb, po, n_vec, b_is_row, nt, cv, s);
     SMHIP_LAUNCH_CHECK("heavy rows");
     return SMHIP_OK;

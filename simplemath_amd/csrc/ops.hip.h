@@ -62,13 +62,8 @@ SMHIP_VEC(uint64_t, 2)
 // contiguous path is touched once, and keeping it out of L2's replacement
 // order is worth ~8 % on the 2R+1W stream (profiles/r01_sweep_stream_add.txt).
 // (Macros, not function templates: a template parameter would strip vec_t's reduced alignment.)
-#ifdef SMHIP_CACHED_STREAMS  // experiment switch (tools/chain_exp.py): plain cached accesses everywhere
-#define load_stream(ptr) (*(ptr))
-#define store_stream(ptr, ...) (*(ptr) = (__VA_ARGS__))
-#else
 #define load_stream(ptr) __builtin_nontemporal_load(ptr)
 #define store_stream(ptr, ...) __builtin_nontemporal_store((__VA_ARGS__), (ptr))
-#endif
 // The READ side's policy as a launch-time (wave-uniform) choice.  Whether a read stream wants `nt` depends on its size
 // (tools/sweep_scalar2.hip, profiles/r02_sweep_scalar2.txt): operands that together fit the 256 MiB Infinity Cache are
 // served faster through plain loads -- 1R+1W at 256 MiB: 92.9 % of HBM peak against 83.5 % with nt, 2R+1W at 2 x 64 MiB:
@@ -136,15 +131,11 @@ SMHIP_VEC(uint64_t, 2)
             asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(smhip_q_), "v"(smhip_w_));   \
         }                                                                                          \
     } while (0)
-#ifdef SMHIP_STORES_ALWAYS_NT  // experiment switch: no branch, no plain arm
-#define store_stream_if(T, ptr, value, pol) store_stream_as(T, ptr, value, true)
-#else
 #define store_stream_if(T, ptr, value, pol)                                                        \
     do {                                                                                           \
         if ((pol) & ::smhip::dev::kStoreKeep) store_stream_as(T, ptr, value, false);              \
         else store_stream_as(T, ptr, value, true);                                                 \
     } while (0)
-#endif
 
 // -------------------------------------------------------------- Op policies
 // f32/f64: one correctly rounded IEEE operation each (add.h:18-59 etc.);
@@ -328,44 +319,6 @@ template <> struct OpCtx<LogOp<float>> : OpCtx<PowOp<float>> {};
 template <> struct OpCtx<ExpOp<double>> : OpCtx<PowOp<double>> {};
 template <> struct OpCtx<LogOp<double>> : OpCtx<PowOp<double>> {};
 
-// PowOp<double> for the flat tile kernel: the same arithmetic reading its tables from BANK-PRIVATE replicas (sm_pow64.h:
-// TabBanked), so that a wave's scattered lookups never collide.  Round 2's scalar-exponent kernel spent 43 % of its
-// LDS-active cycles in bank conflicts and ran at 68 % of HBM peak on random bases against 78 % when every lane hit the same
-// entry.  Sixteen replicas of the five table arrays are 80 KiB of LDS: the kernel runs 1024-thread workgroups (two per
-// CU, 64 VGPRs: full occupancy) and each thread stages ten doubles.  Only launched by contiguous.hip's heavy form; every
-// other kernel keeps PowOp<double> and its 5 KiB copy.
-struct PowBanked {
-    static __device__ __forceinline__ double apply(double a, double b) { return PowOp<double>::apply(a, b); }
-};
-template <> struct OpCtx<PowBanked> {
-    static constexpr int kDoubles = smpow64::kBankedDoubles;
-    smpow64::TabBanked tab;
-    template <int BLOCK> struct Stage { double v[kDoubles / BLOCK]; };
-    __device__ __forceinline__ void init() {  // (the tile kernel uses fetch / commit)
-        __shared__ __attribute__((aligned(16))) double lds_tab[kDoubles];
-        for (int f = threadIdx.x; f < kDoubles; f += blockDim.x) lds_tab[f] = smpow64::table_value((f >> 4) / smpow64::kN, (f >> 4) % smpow64::kN);
-        __syncthreads();
-        tab.mine = lds_tab + (threadIdx.x & (smpow64::kBankedReplicas - 1));
-    }
-    // flat slot f = (array * 128 + entry) * 16 + replica: thread t stages slots t, t + BLOCK, ... -- consecutive lanes write
-    // consecutive doubles (conflict-free), and the sixteen lanes that share a source value read it as one broadcast
-    template <int BLOCK> __device__ __forceinline__ void fetch(Stage<BLOCK> &st) const {
-        static_assert(kDoubles % BLOCK == 0, "the replicas are staged in whole rounds");
-#pragma unroll
-        for (int k = 0; k < kDoubles / BLOCK; ++k) {
-            const int f = (int)threadIdx.x + k * BLOCK;
-            st.v[k] = smpow64::table_value((f >> 4) / smpow64::kN, (f >> 4) % smpow64::kN);
-        }
-    }
-    template <int BLOCK> __device__ __forceinline__ void commit(const Stage<BLOCK> &st) {
-        __shared__ __attribute__((aligned(16))) double lds_tab[kDoubles];
-#pragma unroll
-        for (int k = 0; k < kDoubles / BLOCK; ++k) lds_tab[(int)threadIdx.x + k * BLOCK] = st.v[k];
-        __syncthreads();
-        tab.mine = lds_tab + (threadIdx.x & (smpow64::kBankedReplicas - 1));
-    }
-};
-
 // sm::pow(a, s) on doubles with ONE exponent of moderate magnitude (sm_pow64.h: pow_core_u; LEVEL 1: |s| <= 1024, 2: |s| <= 16):
 // the general arithmetic minus what only an unknown exponent needs.  Launched by contiguous.hip's array-scalar form.  The tables
 // sit in LDS as five plain arrays (5 KiB; sm_pow64.h: TabSoA).
@@ -435,8 +388,6 @@ __device__ __forceinline__ void apply_n(const OpCtx<Op> &ctx, const T (&a)[W], c
         smunary::exp_n<W>(a, r, smpow64::TabAoS{ctx.logtab, ctx.exptab});
     } else if constexpr (std::is_same<Op, LogOp<double>>::value) {
         smunary::log_n<W>(a, r, smpow64::TabAoS{ctx.logtab, ctx.exptab});
-    } else if constexpr (std::is_same<Op, PowBanked>::value) {
-        smpow64::pow_n<W, smpow64::TabBanked>(a, b, r, ctx.tab);
     } else if constexpr (HalfIntOf<Op>::value != 0) {
         smpow64::pow_halfint_n<W, HalfIntOf<Op>::value>(a, HalfIntOf<Op>::value, r);
     } else if constexpr (ScalarLevelOf<Op>::value != 0) {

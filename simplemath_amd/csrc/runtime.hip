@@ -393,8 +393,7 @@ int OpScope::begin(const Span *reads, size_t n_reads, Span write, hipStream_t *s
     // previous such operator did not
     const bool edge0 = need[1] > d.synced[0][1], edge1 = need[0] > d.synced[1][0];  // what running on queue 0 / 1 would have to wait for
     int q;
-    static const size_t overlap_max = [] { const char *e = getenv("SMHIP_OVERLAP_MAX_MIB"); return e && *e ? (size_t)atol(e) << 20 : kOverlapMaxBytes; }();  // experiments
-    if (bytes > overlap_max) q = 0;
+    if (bytes > kOverlapMaxBytes) q = 0;
     else if (edge0 != edge1) q = edge0 ? 1 : 0;
     else if (!edge0) { q = d.last ^ 1; d.last = q; ++d.alternations; }
     else q = 0;

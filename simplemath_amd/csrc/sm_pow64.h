@@ -356,10 +356,7 @@ SM_POW_FN double fma4_c(double r, double c) {
 //              of them): three LDS reads per element, and across a wave's scattered indices they collide -- entry i starts
 //              in bank 6 i mod 32, so 64 random lookups share 16 starting banks (43 % of the LDS-active cycles of the
 //              scalar-exponent kernel were bank conflicts, profiles/r02_pow64_rate.txt).
-//   TabBanked  sixteen replicas of every value, one per PAIR OF BANKS: value (array a, entry i) for replica c lives at
-//              double index (a * 128 + i) * 16 + c, lane l reads replica l mod 16 -- whatever the indices, sixteen
-//              neighbouring lanes hit sixteen different bank pairs: no lookup can conflict.  80 KiB of LDS, so the kernel
-//              that uses it runs 1024-thread workgroups, two per CU (ops.hip.h: PowBanked).
+//   TabSoA     five plain arrays in LDS, one per value (below, with the one-exponent form that reads them).
 #if defined(__HIPCC__)
 #define SM_POW_MEMFN __host__ __device__ __forceinline__
 #else
@@ -372,15 +369,6 @@ struct TabAoS {
     SM_POW_MEMFN double logctail(int i) const { return logtab[3 * i + 2]; }
     SM_POW_MEMFN double th(int j) const { return exptab[2 * j]; }
     SM_POW_MEMFN double trel(int j) const { return exptab[2 * j + 1]; }
-};
-constexpr int kBankedReplicas = 16, kBankedArrays = 5, kBankedDoubles = kBankedArrays * kN * kBankedReplicas;
-struct TabBanked {
-    const double *mine;  // the LDS copy + (lane & 15)
-    SM_POW_MEMFN double invc(int i) const { return mine[(0 * kN + i) * kBankedReplicas]; }
-    SM_POW_MEMFN double logc(int i) const { return mine[(1 * kN + i) * kBankedReplicas]; }
-    SM_POW_MEMFN double logctail(int i) const { return mine[(2 * kN + i) * kBankedReplicas]; }
-    SM_POW_MEMFN double th(int j) const { return mine[(3 * kN + j) * kBankedReplicas]; }
-    SM_POW_MEMFN double trel(int j) const { return mine[(4 * kN + j) * kBankedReplicas]; }
 };
 // value `a` (0 invc, 1 logc_hi, 2 logc_lo, 3 T, 4 tail) of entry i, from the generated tables
 SM_POW_FN double table_value(int a, int i) { return a < 3 ? kLogTab[3 * i + a] : kExpTab[2 * i + (a - 3)]; }

@@ -101,9 +101,8 @@ int launch_unary_dense(int fn, int dtype, const void *a, size_t n, void *out, hi
     // The functions that look a table up in LDS take pow's tile kernel from 2^16 elements on (contiguous.hip:
     // launch_unary_tiles): with one vector per lane every 4 KiB of data paid for staging 2-5 KiB of table -- the f64 exp / log ran
     // at 57 % of HBM peak, the f32 log at 68 % (profiles/unary_rates.txt has both forms).  The same Op, the same bits.
-    static const bool tiles = [] { const char *e = getenv("SMHIP_UNARY_TILES"); return !(e && *e && atoi(e) == 0); }();  // experiments
     const bool table = (dtype == SMHIP_F32 && fn == SMHIP_UNARY_LOG) || (dtype == SMHIP_F64 && (fn == SMHIP_UNARY_EXP || fn == SMHIP_UNARY_LOG));
-    if (tiles && table && n >= ((size_t)1 << 16)) return launch_unary_tiles(fn, dtype, a, n, out, s);
+    if (table && n >= ((size_t)1 << 16)) return launch_unary_tiles(fn, dtype, a, n, out, s);
     switch (dtype) {
         case SMHIP_F32: return run_dense_fn<float>(fn, a, out, n, s);
         case SMHIP_F64: return run_dense_fn<double>(fn, a, out, n, s);

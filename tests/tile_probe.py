@@ -99,10 +99,10 @@ for dt, bar in ((np.float32, 1), (np.float64, 1)):
                 print("MISMATCH pow", np.dtype(dt), dims, int(d.max()))
                 sys.exit(1)
             cases += 1
-# output rows off the 128-byte lines (inner extents like 1031): with the wide patch (SMHIP_TILE_QB=1024, or unforced past the
-# Infinity Cache) these take tile_shift_body -- patch rows cut at the output's LINES, each row at its own shift.  One and two
+# output rows off the 128-byte lines (inner extents like 1031): every patch row starts and ends inside a line it shares with
+# the neighbouring patch, under each forced patch width (SMHIP_TILE_QB) and walk.  One and two
 # turned operands, either side, non-commutative Ops, slices of a third axis, operand views at offset bases, a constant direct
-# operand (column), every element type; extents around the patch sizes so that the first / last windows hang over the rows' ends.
+# operand (column), every element type; extents around the patch sizes so that the last patch of a row and of a column is partial.
 for t, dims in enumerate(((300, 1031), (257, 517), (1000, 773), (3, 260, 1029), (512, 2049), (640, 1283), (259, 514), (2, 300, 643), (1030, 1030))):
     dtn = ("f32", "f64", "i32")[t % 3]
     dt = DT[dtn]
@@ -141,7 +141,7 @@ for t, dims in enumerate(((300, 1031), (257, 517), (1000, 773), (3, 260, 1029), 
         cases += 2
     cases += 1
 if len(sys.argv) > 1 and sys.argv[1] == "big":
-    # 8191 x 8703 f32 = 272 MiB per array, rows off the lines: unforced, the wide patch with shifted rows
+    # 8191 x 8703 f32 = 272 MiB per array, unforced: the wide patch, row-major walk, rows off the lines
     P, Q = 8191, 8703
     a = gen.gen(np.float32, P * Q, 3, "uniform").reshape(Q, P)
     b = gen.gen(np.float32, P * Q, 4, "uniform").reshape(P, Q)
