@@ -91,6 +91,7 @@ struct FusionStats {
     unsigned long long summed_chains = 0;       // `(<expression>).sum()` taken in the chain's own pass, the value never written
     unsigned long long reductions = 0;          // axis reductions (smhip_reduce_axes: sum / mean / max / min along axes)
     unsigned long long scans = 0;               // cumulative scans (smhip_scan_axis: cumsum / cumprod / cummax / cummin)
+    unsigned long long arg_reductions = 0;      // smhip_argreduce_axis calls: argmax / argmin / max_with_index / min_with_index
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -742,6 +743,20 @@ public:
     SMArray cummax() const { return scan_flat(SMHIP_SCAN_MAX); }
     SMArray cummin() const { return scan_flat(SMHIP_SCAN_MIN); }
 
+    // WHERE the maximum / minimum along an axis stands (np.argmax / np.argmin): positions along `axis` as std::int64_t, the
+    // first one on a tie (-0 == +0) and the first NaN if the axis holds one; resident on the device.  `axis` counts from the
+    // end when negative, an axis out of range throws std::runtime_error, keepdims keeps the axis as an extent of 1.  Without
+    // an axis the result is the row-major index into this array, shape {1} (a view that is not dense is copied dense first).
+    // A pending operator chain as the operand is evaluated first, a transposed view is read in place; ONE
+    // smhip_argreduce_axis call (counted in sm::fusion_stats().arg_reductions).  max_with_index / min_with_index give
+    // {the extreme itself, its position} from the same single pass; the value is exactly the element at that position.
+    SMArray<std::int64_t> argmax(int axis, bool keepdims = false) const { return arg_along(SMHIP_ARG_MAX, axis, keepdims, nullptr); }
+    SMArray<std::int64_t> argmin(int axis, bool keepdims = false) const { return arg_along(SMHIP_ARG_MIN, axis, keepdims, nullptr); }
+    SMArray<std::int64_t> argmax() const { return arg_flat(SMHIP_ARG_MAX); }
+    SMArray<std::int64_t> argmin() const { return arg_flat(SMHIP_ARG_MIN); }
+    std::pair<SMArray, SMArray<std::int64_t>> max_with_index(int axis, bool keepdims = false) const { return arg_with_value(SMHIP_ARG_MAX, axis, keepdims); }
+    std::pair<SMArray, SMArray<std::int64_t>> min_with_index(int axis, bool keepdims = false) const { return arg_with_value(SMHIP_ARG_MIN, axis, keepdims); }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -1005,6 +1020,53 @@ private:
         const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
         hip::check(smhip_scan_axis(kind, hip::dtype_of<T>::id, in, &n, &one, 1, 0, out.device_data_mut()));
         ++detail::tls_fusion_stats.scans;
+        return out;
+    }
+
+    int arg_axis(int axis) const {
+        const int nd = static_cast<int>(_shape.size());
+        const int a = axis < 0 ? axis + nd : axis;
+        if (a < 0 || a >= nd) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(axis) + " out of range for rank " + std::to_string(nd));
+        return a;
+    }
+    std::vector<std::size_t> arg_shape(int axis, bool keepdims) const {
+        const int a = arg_axis(axis);
+        std::vector<std::size_t> shape;
+        for (int d = 0; d < static_cast<int>(_shape.size()); ++d) {
+            if (d != a) shape.push_back(_shape[d]);
+            else if (keepdims) shape.push_back(1);
+        }
+        if (shape.empty()) shape.push_back(1);
+        return shape;
+    }
+    std::pair<SMArray, SMArray<std::int64_t>> arg_with_value(int kind, int axis, bool keepdims) const {
+        SMArray values = device_empty(arg_shape(axis, keepdims));
+        SMArray<std::int64_t> where = arg_along(kind, axis, keepdims, &values);
+        return {std::move(values), std::move(where)};
+    }
+    // `values`: a dense array of the result's shape for the extremes themselves, or nullptr.
+    SMArray<std::int64_t> arg_along(int kind, int axis, bool keepdims, SMArray *values) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "argmax / argmin: f32, f64, i32 and i64");
+        const int a = arg_axis(axis);
+        hip::DeviceGuard on(device());
+        const T *in = device_data();  // a pending chain that produces this operand runs here
+        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(arg_shape(axis, keepdims));
+        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
+        hip::check(smhip_argreduce_axis(kind, hip::dtype_of<T>::id, in, sh.data(), st.data(), static_cast<int>(sh.size()), a, out.device_data_mut(),
+                                        values ? values->device_data_mut() : nullptr));
+        ++detail::tls_fusion_stats.arg_reductions;
+        return out;
+    }
+    // The elements in row-major order as one row: a view is made dense first.
+    SMArray<std::int64_t> arg_flat(int kind) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "argmax / argmin: f32, f64, i32 and i64");
+        hip::DeviceGuard on(device());
+        std::unique_ptr<SMArray> holder;
+        const T *in = dense_device(holder);
+        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{1});
+        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
+        hip::check(smhip_argreduce_axis(kind, hip::dtype_of<T>::id, in, &n, &one, 1, 0, out.device_data_mut(), nullptr));
+        ++detail::tls_fusion_stats.arg_reductions;
         return out;
     }
 

@@ -245,6 +245,23 @@ SMArray<T> cummin(const SMArray<T> &arr, int axis) { return arr.cummin(axis); }
 template <typename T>
 SMArray<T> cummin(const SMArray<T> &arr) { return arr.cummin(); }
 
+// Where the maximum / minimum stands (np.argmax / np.argmin): SMArray<std::int64_t> of positions along `axis` (negative
+// counts from the end; keepdims keeps it as an extent of 1), the first on a tie and the first NaN if there is one; without
+// an axis the row-major index of the whole array, shape {1}.  max_with_index / min_with_index return {values, positions}
+// from ONE pass over the operand.  Semantics as SMArray::argmax(axis) (SMArray.h) and smhip_argreduce_axis (smhip.h).
+template <typename T>
+SMArray<std::int64_t> argmax(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.argmax(axis, keepdims); }
+template <typename T>
+SMArray<std::int64_t> argmax(const SMArray<T> &arr) { return arr.argmax(); }
+template <typename T>
+SMArray<std::int64_t> argmin(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.argmin(axis, keepdims); }
+template <typename T>
+SMArray<std::int64_t> argmin(const SMArray<T> &arr) { return arr.argmin(); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> max_with_index(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.max_with_index(axis, keepdims); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> min_with_index(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.min_with_index(axis, keepdims); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

@@ -355,6 +355,42 @@ int smhip_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, co
 int smhip_scan_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
                     int *route, int *launches, int64_t *ori3, int64_t *chunk);
 
+/* ------------------------------------------------------- argmax / argmin */
+/* np.argmax / np.argmin along ONE axis: index_out[o, i] = the position r along `axis`, in [0, shape[axis]), of the extreme of
+ * a[o, r, i] over r, as int64_t.  The contract is numpy's:
+ *   along the axis       ARG_MAX                                        ARG_MIN
+ *   no NaN               the smallest r whose element is >= every       the smallest r whose element is <= every other
+ *                        other (-0.0 == +0.0: ties go to the first)
+ *   a NaN (f32, f64)     the smallest r whose element is NaN            the same
+ *   pairs (v, r)         a NaN beats a non-NaN; among two NaNs, or two equal values, the smaller r wins; otherwise the
+ *                        larger v wins                                  ... the smaller v wins
+ * That combine is associative and commutative, so the result is bit-exact and the same on every run, whatever the partition
+ * of the work.  value_out, when given, receives exactly a[..., index, ...]: the bits of the winning element (which zero,
+ * which NaN), so "max and where" is one pass. */
+typedef enum smhip_arg_kind { SMHIP_ARG_MAX = 0, SMHIP_ARG_MIN = 1 } smhip_arg_kind;
+/* `a` is any view (strides in ELEMENTS, >= 0; rank 1 .. SMHIP_MAX_NDIM; f32, f64, i32 or i64).  index_out is dense row-major
+ * over the axes other than `axis`, in their order (1 element when ndim == 1); value_out_or_null, when not NULL, has the same
+ * layout in the element type.  Arguments are checked before any device is touched (SMHIP_ERR_INVALID): kind, dtype, ndim,
+ * axis outside [0, ndim) (not counted from the end), negative extents or strides, null a / shape / strides / index_out,
+ * index_out or value_out overlapping a's span or each other, and shape[axis] == 0 while the result is not empty (as numpy
+ * raises).  Any other extent of 0 is a no-op, whatever the pointers.  Asynchronous, stream-ordered; recorded tiny operators
+ * are flushed first. */
+int smhip_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim,
+                         int axis, int64_t *index_out, void *value_out_or_null);
+/* Host only, no device touched: the route smhip_argreduce_axis would take.  *route = a kernel id (SMHIP_ARG_ROUTE_*) ORed
+ * with the flags below; *launches = the kernel launches of the whole call; ori3 = {O, R, I} after merging
+ * (out[o, i] = arg_r a[o*so + r*sr + i*si]; R is exactly shape[axis]); *chunk = the length of the chunks R is cut into (R
+ * itself when it is not).  Any output may be NULL.  The planner's test hook. */
+#define SMHIP_ARG_ROUTE_NONE 0    /* nothing to compute: the result is empty */
+#define SMHIP_ARG_ROUTE_ROW 1     /* I = 1, sr = 1: each row of R elements contiguous */
+#define SMHIP_ARG_ROUTE_COLUMN 2  /* si = 1: a lane owns 4 consecutive kept columns and walks R */
+#define SMHIP_ARG_SPLIT 0x100     /* R cut into fixed chunks (the shape decides); each chunk's (value, index) pair is folded by
+                                     a finishing launch (two when a row has more than 4096 chunks) */
+#define SMHIP_ARG_COPY 0x200      /* the operand is copied dense first (no unit stride in the walk, a stride-0 axis, kept axes
+                                     that do not merge to one outer and one inner) */
+int smhip_argreduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                         int *route, int *launches, int64_t *ori3, int64_t *chunk);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

@@ -43,6 +43,11 @@ SCAN_KINDS = {"cumsum": SCAN_SUM, "cumprod": SCAN_PROD, "cummax": SCAN_MAX, "cum
 # smhip_scan_plan's route word: a kernel id in the low byte, flags above it
 SCAN_ROUTE_NONE, SCAN_ROUTE_COPYONLY, SCAN_ROUTE_ROW, SCAN_ROUTE_COLUMN = range(4)
 SCAN_SPLIT, SCAN_COPY = 0x100, 0x200
+ARG_MAX, ARG_MIN = range(2)  # smhip_arg_kind
+ARG_KINDS = {"argmax": ARG_MAX, "argmin": ARG_MIN}
+# smhip_argreduce_plan's route word: a kernel id in the low byte, flags above it
+ARG_ROUTE_NONE, ARG_ROUTE_ROW, ARG_ROUTE_COLUMN = range(3)
+ARG_SPLIT, ARG_COPY = 0x100, 0x200
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -600,6 +605,57 @@ class Smhip:
         route, launches, ori, chunk = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), C.c_int64(0)
         self._ck(self.c.smhip_scan_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)),
                                         C.byref(route), C.byref(launches), ori, C.byref(chunk)))
+        return route.value, launches.value, tuple(int(x) for x in ori), chunk.value
+
+    def argreduce(self, kind, a: DeviceArray, axis=None, keepdims=False, values=False, out: DeviceArray | None = None):
+        """np.argmax / np.argmin of `a` (any view) along `axis` ("argmax", "argmin" or the smhip_arg_kind value) -> a new dense
+        int64 DeviceArray of positions along the axis, or into `out`, which must be a dense int64 array with as many elements
+        as the result (its shape is not changed).  values=True returns (values, indices) from the same single pass, the values
+        being exactly the elements at those positions.  axis=None gives the row-major index of the whole view, shape (1,) (a
+        DeviceArray has no 0-d form); a view that is not dense is copied dense first."""
+        kind = ARG_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if a.dtype not in DTYPES:
+            raise ValueError(f"argreduce: dtype {a.dtype} (f32, f64, i32 and i64 only)")
+        if axis is None:
+            if not a.is_dense():  # the row-major order of a view: its dense copy
+                dense = self.empty(a.shape, a.dtype)
+                self.assign(dense, a)
+                a = dense
+            shape, strides, axis = (a.size,), (1,), 0
+            result_shape = (1,) * a.ndim if keepdims else (1,)
+        else:
+            (axis,) = self._axes(a.ndim, int(axis))
+            shape, strides = a.shape, a.strides
+            if keepdims:
+                result_shape = tuple(1 if d == axis else n for d, n in enumerate(a.shape))
+            else:
+                result_shape = tuple(n for d, n in enumerate(a.shape) if d != axis) or (1,)
+        count = int(np.prod(result_shape, dtype=np.int64))
+        if out is None:
+            out = self.empty(result_shape, np.int64)
+        elif out.dtype != np.dtype(np.int64) or out.size != count or not out.is_dense():
+            raise ValueError(f"argreduce: out must be a dense int64 array of {count} elements (shape {tuple(result_shape)}); "
+                             f"got {out.dtype} {out.shape} dense={out.is_dense()}")
+        vals = self.empty(result_shape, a.dtype) if values else None
+        self._ck(self.c.smhip_argreduce_axis(C.c_int(kind), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(shape), _i64(strides),
+                                             C.c_int(len(shape)), C.c_int(axis), C.c_void_p(out.ptr), C.c_void_p(vals.ptr if values else 0)))
+        return (vals, out) if values else out
+
+    def argreduce_raw(self, kind, dtype, a_ptr, shape, strides, axis, index_ptr, value_ptr=0, ndim=None):
+        """smhip_argreduce_axis with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        return self.c.smhip_argreduce_axis(C.c_int(kind), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                           _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_int(axis),
+                                           C.c_void_p(index_ptr), C.c_void_p(value_ptr))
+
+    def argreduce_plan(self, kind, dtype, shape, strides, axis):
+        """smhip_argreduce_plan (host only): (route word, launches, (O, R, I), chunk length) for a call on shape / strides (elements)."""
+        kind = ARG_KINDS[kind] if isinstance(kind, str) else int(kind)
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        route, launches, ori, chunk = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), C.c_int64(0)
+        self._ck(self.c.smhip_argreduce_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)),
+                                             C.byref(route), C.byref(launches), ori, C.byref(chunk)))
         return route.value, launches.value, tuple(int(x) for x in ori), chunk.value
 
     def sum(self, a: DeviceArray):

@@ -229,4 +229,11 @@ void scan_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int
 int launch_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *out,
                      hipStream_t s);
 
+// argreduce_axis.hip: argmax / argmin along an axis (smhip_argreduce_axis); the checks and the planner are host-only
+int argreduce_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis);
+void argreduce_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
+                         int64_t *chunk);
+int launch_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                          int64_t *index_out, void *value_out, hipStream_t s);
+
 }  // namespace smhip

@@ -34,6 +34,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "axis_plan.h"
 #include "fold.hip.h"
 #include "internal.h"
 #include "ops.hip.h"
@@ -293,7 +294,9 @@ struct Plan {
 
 int vec_width(int dtype) { return dtype == SMHIP_F64 || dtype == SMHIP_I64 ? 2 : 4; }
 
-struct Ax { int64_t n, st, ost; bool red; };
+using axis_plan::Ax;  // axis_plan.h: the merging of axes, shared with argreduce_axis.hip
+using axis_plan::merge_axes;
+using axis_plan::row_major;
 
 // Splits and row segments of one canonical pass; counts its launches.
 void shape_pass(Pass &p, int dtype, int *launches) {
@@ -361,42 +364,6 @@ bool single_pass(const Ax *ax, int n, Pass *p) {
     else if (q.I > 1 && q.si == 1) q.route = q.I <= kChannelMax && q.sr == q.I && q.R >= kChannelMinR ? kRouteChannel : kRouteColumn;
     else return false;
     *p = q;
-    return true;
-}
-
-// Axes of extent > 1, ordered by stride (largest first, ties in index order), neighbours merged where memory -- and for kept
-// axes the dense result -- runs on without a gap.  Returns the count.
-int merge_axes(const int64_t *shape, const int64_t *strides, int ndim, uint32_t mask, bool by_index, Ax *ax) {
-    int64_t ost[SMHIP_MAX_NDIM];
-    int64_t acc = 1;
-    for (int d = ndim - 1; d >= 0; --d) {
-        ost[d] = 0;
-        if (!(mask >> d & 1)) ost[d] = acc, acc *= shape[d];
-    }
-    int n = 0;
-    for (int d = 0; d < ndim; ++d)
-        if (shape[d] > 1) ax[n++] = Ax{shape[d], strides[d], ost[d], (mask >> d & 1) != 0};
-    if (!by_index) std::stable_sort(ax, ax + n, [](const Ax &x, const Ax &y) { return x.st > y.st; });
-    int m = 0;
-    for (int k = 0; k < n; ++k) {
-        if (m > 0) {
-            Ax &prev = ax[m - 1];
-            if (prev.red == ax[k].red && prev.st == ax[k].st * ax[k].n && (prev.red || prev.ost == ax[k].ost * ax[k].n)) {
-                prev.n *= ax[k].n, prev.st = ax[k].st, prev.ost = ax[k].ost;
-                continue;
-            }
-        }
-        ax[m++] = ax[k];
-    }
-    return m;
-}
-
-bool row_major(const int64_t *shape, const int64_t *strides, int ndim) {
-    int64_t acc = 1;
-    for (int d = ndim - 1; d >= 0; --d) {
-        if (shape[d] != 1 && strides[d] != acc) return false;
-        acc *= shape[d];
-    }
     return true;
 }
 

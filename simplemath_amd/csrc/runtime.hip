@@ -1486,6 +1486,37 @@ int smhip_scan_plan(int kind, int dtype, const int64_t *shape, const int64_t *st
     return SMHIP_OK;
 }
 
+int smhip_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, int64_t *index_out,
+                         void *value_out) {
+    if (int rc = argreduce_axis_check("argreduce_axis", kind, dtype, shape, strides, ndim, axis)) return rc;
+    int64_t nout = 1;
+    for (int d = 0; d < ndim; ++d)
+        if (d != axis) nout *= shape[d];
+    if (nout == 0) return SMHIP_OK;
+    if (!a || !index_out) return fail(SMHIP_ERR_INVALID, "argreduce_axis: null buffer");
+    const size_t esz = dtype_size(dtype);
+    const Span sa{a, span_bytes(shape, strides, ndim, esz)}, si{index_out, (size_t)nout * sizeof(int64_t)}, sv{value_out, value_out ? (size_t)nout * esz : 0};
+    auto overlap = [](Span x, Span y) {
+        const char *x0 = static_cast<const char *>(x.p), *y0 = static_cast<const char *>(y.p);
+        return x.bytes && y.bytes && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
+    };
+    if (overlap(si, sa) || overlap(sv, sa) || overlap(si, sv))
+        return fail(SMHIP_ERR_INVALID, "argreduce_axis: index_out / value_out overlap the operand or each other");
+    // the operand's span and the index result are declared; the call still orders itself behind everything and everything
+    // later behind it (a pooled copy, the chunks' pairs and value_out are not declared), recorded tiny operators flushed first
+    hipStream_t s;
+    OpScope op_scope_;
+    if (int rc = op_scope_.begin(&sa, 1, si, &s, true)) return rc;
+    return launch_argreduce_axis(kind, dtype, a, shape, strides, ndim, axis, index_out, value_out, s);
+}
+
+int smhip_argreduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches,
+                         int64_t *ori3, int64_t *chunk) {
+    if (int rc = argreduce_axis_check("argreduce_plan", kind, dtype, shape, strides, ndim, axis)) return rc;
+    argreduce_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
+    return SMHIP_OK;
+}
+
 int smhip_sum(int dtype, const void *a, size_t n, double *out_host) {
     if (!out_host) return fail(SMHIP_ERR_INVALID, "sum: null result");
     void *h = nullptr, *d = nullptr;

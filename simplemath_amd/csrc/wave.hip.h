@@ -67,6 +67,20 @@ template <typename A, typename F> __device__ __forceinline__ A segment_fold(A v,
     return v;
 }
 
+// segment_fold for PAIRS (argreduce_axis.hip: a value and where it stands): both halves go through the SAME DPP controls, so a
+// lane always meets the pair of one source lane, and `take(v, r, mv, mr)` then replaces (v, r) by (mv, mr) where the pair
+// combine prefers it.  Lanes without a source meet (idv, idr), which `take` never prefers.  The combine is associative, so as
+// in segment_fold the segment's pair is valid in its LAST lane; it is commutative and idempotent too, so the windows that
+// reach over a segment's start in between do no harm.
+template <typename V, typename R, typename F> __device__ __forceinline__ void segment_fold_pair(V &v, R &r, int g, V idv, R idr, F take) {
+    if (g >= 2) take(v, r, dpp_move_or<0x111, 0xf>(v, idv), dpp_move_or<0x111, 0xf>(r, idr));
+    if (g >= 4) take(v, r, dpp_move_or<0x112, 0xf>(v, idv), dpp_move_or<0x112, 0xf>(r, idr));
+    if (g >= 8) take(v, r, dpp_move_or<0x114, 0xf>(v, idv), dpp_move_or<0x114, 0xf>(r, idr));
+    if (g >= 16) take(v, r, dpp_move_or<0x118, 0xf>(v, idv), dpp_move_or<0x118, 0xf>(r, idr));
+    if (g >= 32) take(v, r, dpp_move_or<0x142, 0xa>(v, idv), dpp_move_or<0x142, 0xa>(r, idr));
+    if (g >= 64) take(v, r, dpp_move_or<0x143, 0xc>(v, idv), dpp_move_or<0x143, 0xc>(r, idr));
+}
+
 // The same moves as an inclusive SCAN (scan_axis.hip): after it lane i holds f over lanes s*g .. i of its segment of g lanes
 // (g = 1, 2, 4, ..., 64, wave-uniform; `lane` = the lane's number in the wave), earlier lanes on the left of f.  A step whose
 // source lies in the segment before is skipped, so every lane's value is valid, not only the segment's last.  Every value
