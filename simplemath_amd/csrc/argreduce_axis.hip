@@ -7,13 +7,13 @@
 // That combine is associative, commutative and idempotent, so the result -- index and value bits -- is the same whatever the
 // partition of the work: no ordering has to be kept between lanes, waves, chunks or launches.
 //
-// Planner (host only; smhip_argreduce_plan reports it).  The merging of reduce_axis.hip (axis_plan.h): size-1 axes dropped,
+// Planner (host only; smhip_argreduce_plan reports it), by the shared rules of axis_plan.h.  Its merging: size-1 axes dropped,
 // the rest ordered by stride, kept neighbours that are adjacent in memory and in the result merged.  The named axis is the
 // only reduced one, so R is exactly that axis and r needs no unravelling.  [kept] R [kept] with a unit stride is the canonical
 //     out[o, i] = arg_r a[o*so + r*sr + i*si]          (O, R, I)
 // so argmax(A.T, 0) is the walk of argmax(A, 1).  A walk with no unit stride, a stride-0 axis, or kept axes that do not merge
 // to one outer and one inner: the operand is copied dense first (smhip_copy_strided's kernels) and planned again.
-// Routes, shaped like those of reduce_axis.hip (16-byte vector loads at any element-aligned address):
+// Routes (16-byte vector loads at any element-aligned address; segments and splits by axis_plan.h's rules, no chunk longer than 2^31):
 //   ROW      I = 1, sr = 1.  Rows of at most 64 loads: a SEGMENT of g = 4, 16 or 64 lanes per row, four rows per segment in
 //            flight.  Longer rows: a wave per (row, chunk), four vectors per lane in flight.
 //   COLUMN   si = 1.  A lane owns 4 consecutive kept columns and walks R, four rows in flight; lanes packed over (o, chunk, quad).
@@ -41,17 +41,12 @@ namespace smhip {
 namespace {
 
 using namespace dev;
+using namespace axis_plan;  // kBlock, kRowsInFlight, OutMap and the planner's rules
 
-constexpr int kBlock = 256;
-constexpr int kRowsInFlight = 4;
-constexpr int64_t kTargetLanes = (int64_t)1 << 18;  // lanes a launch should have before R is split (256 CUs x 1024), as the reductions
 constexpr int64_t kMaxChunk = (int64_t)1 << 31;     // a chunk's positions fit 32 bits
 constexpr int64_t kFinishWhole = 4096, kFinishRun = 1024;  // partials a finishing wave folds: a whole row up to 4096, else runs of 1024
 constexpr uint32_t kEmpty32 = 0xffffffffu;          // the position of a lane that holds no element: never preferred
 constexpr int64_t kEmpty64 = std::numeric_limits<int64_t>::max();
-
-// Where a launch's results go: out[o*oso + i*osi + c*ocs] (c = the chunk of R; 0 when R is not split).
-struct OutMap { int64_t oso, osi, ocs; };
 
 // The value no element is worse than; beside kEmpty it is the pair fold's identity.
 template <typename T, bool MAX> __device__ __forceinline__ T worst() { return identity<T, MAX ? kMax : kMin>(); }
@@ -270,53 +265,32 @@ __global__ __launch_bounds__(kBlock) void finish_kernel(const T *__restrict__ pv
 }
 
 // ------------------------------------------------------------------------------------------------------ the planner
-struct Plan {
+struct Plan : Canon {
     int route = SMHIP_ARG_ROUTE_NONE;
     bool copy = false;
     int launches = 0;
-    int64_t O = 1, R = 1, I = 1, so = 0, sr = 1, si = 1;
-    int64_t oso = 1, osi = 1;  // where result (o, i) goes: out[o*oso + i*osi]
     int64_t C = 1, CL = 0;     // chunks of R (C > 1: finishing launches) and their length
     int g = 0;                 // ROW: lanes per row (4, 16, 64), 0 = a wave per (row, chunk)
     int64_t total = 0, nout = 0;
     int code() const { return route | (C > 1 ? SMHIP_ARG_SPLIT : 0) | (copy ? SMHIP_ARG_COPY : 0); }
 };
 
-int vec_width(int dtype) { return dtype == SMHIP_F64 || dtype == SMHIP_I64 ? 2 : 4; }
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// Splits and row segments, as reduce_axis.hip shapes its passes; a chunk is never longer than kMaxChunk.
+// Splits and row segments; a chunk is never longer than kMaxChunk, and an unsplit walk's chunk is R.
 void shape_plan(Plan &p, int dtype) {
     const int64_t W = vec_width(dtype);
-    p.C = 1, p.CL = p.R;
+    Split sp{1, 0};
     if (p.route == SMHIP_ARG_ROUTE_ROW) {
-        const int64_t nvec = p.R / W, tail = p.R - nvec * W;
-        if (nvec + tail <= 64) {
-            p.g = nvec + tail <= 4 ? 4 : nvec + tail <= 16 ? 16 : 64;
-        } else {
-            const int64_t unit = 4 * 64 * W;  // one guard-free step of a wave
-            const int64_t lanes = p.O * 64;
-            int64_t want = lanes < kTargetLanes ? std::min(ceil_div(kTargetLanes, lanes), ceil_div(p.R, unit)) : 1;
-            want = std::max(want, ceil_div(p.R, kMaxChunk));
-            if (want > 1) {
-                p.CL = ceil_div(ceil_div(p.R, want), unit) * unit;
-                p.C = ceil_div(p.R, p.CL);
-            }
-        }
+        p.g = segment_lanes(row_loads(p.R, W));
+        if (p.g == 0) sp = split_row(p.O * 64, p.R, 4 * 64 * W, kMaxChunk);  // unit: one guard-free step of a wave
     } else {
-        const int64_t lanes = p.O * ceil_div(p.I, 4);
-        int64_t want = lanes < kTargetLanes ? std::min(ceil_div(kTargetLanes, lanes), ceil_div(p.R, 16)) : 1;
-        want = std::max(want, ceil_div(p.R, kMaxChunk));
-        if (want > 1) {
-            p.CL = ceil_div(ceil_div(p.R, want), 4) * 4;
-            p.C = ceil_div(p.R, p.CL);
-        }
+        sp = split_column(p.O * ceil_div(p.I, 4), p.R, kMaxChunk);
     }
+    p.C = 1, p.CL = p.R;
+    if (sp.CL) p.C = sp.C, p.CL = sp.CL;
     p.launches = (p.copy ? 1 : 0) + 1 + (p.C > 1 ? (p.C > kFinishWhole ? 2 : 1) : 0);
 }
 
 void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, Plan *pl) {
-    using namespace axis_plan;
     *pl = Plan();
     Plan &p = *pl;
     int64_t before = 1, after = 1;
@@ -331,20 +305,12 @@ void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim
     if (p.total == 0) return;  // nothing to write (R = 0 with a result to write is refused by the checks)
     Ax ax[SMHIP_MAX_NDIM];
     const int n = merge_axes(shape, strides, ndim, 1u << axis, false, ax);
-    int red = -1;
-    for (int k = 0; k < n; ++k)
-        if (ax[k].red) red = k;
-    bool canonical = false;
-    if (!zero_stride && red >= 0 && red <= 1 && n - red - 1 <= 1) {
-        Plan q;
-        q.R = ax[red].n, q.sr = ax[red].st;
-        if (red == 1) q.O = ax[0].n, q.so = ax[0].st, q.oso = ax[0].ost;
-        if (red + 1 < n) q.I = ax[red + 1].n, q.si = ax[red + 1].st, q.osi = ax[red + 1].ost;
-        if (q.I == 1 && q.sr == 1) q.route = SMHIP_ARG_ROUTE_ROW, canonical = true;
-        else if (q.I > 1 && q.si == 1) q.route = SMHIP_ARG_ROUTE_COLUMN, canonical = true;
-        if (canonical) q.total = p.total, q.nout = p.nout, p = q;
-    }
-    if (!canonical) {  // dense in index order (copied there first unless it already is; R = 1 comes here too)
+    Canon c;
+    const Walk walk = zero_stride ? kWalkNone : canonical(ax, n, &c);
+    if (walk != kWalkNone) {
+        static_cast<Canon &>(p) = c;
+        p.route = walk == kWalkRow ? SMHIP_ARG_ROUTE_ROW : SMHIP_ARG_ROUTE_COLUMN;
+    } else {  // dense in index order (copied there first unless it already is; R = 1 comes here too)
         p.copy = zero_stride || !row_major(shape, strides, ndim);
         p.route = after == 1 ? SMHIP_ARG_ROUTE_ROW : SMHIP_ARG_ROUTE_COLUMN;
         p.so = p.R * after, p.sr = after, p.si = 1, p.oso = after, p.osi = 1;
@@ -353,25 +319,14 @@ void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim
 }
 
 // ------------------------------------------------------------------------------------------------------ launching
-// As the reductions: every kernel loops over its tasks, so the grid can be capped below HIP's 32-bit work-item count.
-// SMHIP_ARGREDUCE_GRID_CAP=<workgroups> lowers the cap (the tests run every loop at small sizes with it).
-unsigned grid_cap() {
-    static const int64_t cap = [] {
-        const char *e = getenv("SMHIP_ARGREDUCE_GRID_CAP");
-        const long long v = e && *e ? atoll(e) : 0;
-        return v > 0 && v < ((int64_t)1 << 20) ? (int64_t)v : ((int64_t)1 << 20);
-    }();
-    return (unsigned)cap;
-}
-unsigned capped(int64_t blocks) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, grid_cap())); }
-unsigned blocks_for(int64_t waves) { return capped(ceil_div(waves, kBlock / 64)); }
+const GridCap &grid_cap() { static const GridCap g(getenv("SMHIP_ARGREDUCE_GRID_CAP")); return g; }  // the cap of every launch here, read once
 
 template <typename T, bool MAX>
 int run_plan(const Plan &p, const T *in, int64_t *idx_out, T *val_out, hipStream_t s) {
     const int nt = stream_policy({{in, (size_t)p.total * sizeof(T)}}, {nullptr, 0});
     if (p.route == SMHIP_ARG_ROUTE_ROW && p.g > 0) {
         const int64_t waves = ceil_div(p.O, kRowsInFlight * (64 / p.g));
-        hipLaunchKernelGGL((row_short_kernel<T, MAX>), dim3(blocks_for(waves)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.g, idx_out, val_out, p.oso, nt);
+        hipLaunchKernelGGL((row_short_kernel<T, MAX>), dim3(grid_cap().blocks_for(waves)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.g, idx_out, val_out, p.oso, nt);
         SMHIP_LAUNCH_CHECK("argreduce_axis");
         return SMHIP_OK;
     }
@@ -392,20 +347,20 @@ int run_plan(const Plan &p, const T *in, int64_t *idx_out, T *val_out, hipStream
         fm = OutMap{p.I * p.C, p.C, 1};
     }
     if (p.route == SMHIP_ARG_ROUTE_ROW) {
-        hipLaunchKernelGGL((row_long_kernel<T, MAX>), dim3(blocks_for(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.CL, p.C, fi, fv, fm, nt);
+        hipLaunchKernelGGL((row_long_kernel<T, MAX>), dim3(grid_cap().blocks_for(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.CL, p.C, fi, fv, fm, nt);
     } else {
         const int64_t lanes = p.O * p.C * ceil_div(p.I, 4);
-        hipLaunchKernelGGL((column_kernel<T, MAX>), dim3(capped(ceil_div(lanes, kBlock))), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.sr, p.I, p.CL, p.C, fi, fv, fm, nt);
+        hipLaunchKernelGGL((column_kernel<T, MAX>), dim3(grid_cap().capped(ceil_div(lanes, kBlock))), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.sr, p.I, p.CL, p.C, fi, fv, fm, nt);
     }
     SMHIP_LAUNCH_CHECK("argreduce_axis");
     if (p.C == 1) return SMHIP_OK;
     int64_t C = p.C;
     if (C2 > 0) {  // runs of kFinishRun pairs first: [rows][C] -> [rows][C2]
-        hipLaunchKernelGGL((finish_kernel<T, MAX>), dim3(blocks_for(rows * C2)), dim3(kBlock), 0, s, fv, fi, rows, C, kFinishRun, C2, (int64_t)1, i2, v2, OutMap{C2, 0, 1});
+        hipLaunchKernelGGL((finish_kernel<T, MAX>), dim3(grid_cap().blocks_for(rows * C2)), dim3(kBlock), 0, s, fv, fi, rows, C, kFinishRun, C2, (int64_t)1, i2, v2, OutMap{C2, 0, 1});
         SMHIP_LAUNCH_CHECK("argreduce_axis finish");
         fv = v2, fi = i2, C = C2;
     }
-    hipLaunchKernelGGL((finish_kernel<T, MAX>), dim3(blocks_for(rows)), dim3(kBlock), 0, s, fv, fi, rows, C, C, (int64_t)1, p.I, idx_out, val_out, OutMap{p.oso, p.osi, 0});
+    hipLaunchKernelGGL((finish_kernel<T, MAX>), dim3(grid_cap().blocks_for(rows)), dim3(kBlock), 0, s, fv, fi, rows, C, C, (int64_t)1, p.I, idx_out, val_out, OutMap{p.oso, p.osi, 0});
     SMHIP_LAUNCH_CHECK("argreduce_axis finish");
     return SMHIP_OK;
 }
@@ -420,16 +375,14 @@ int run_kind(int kind, const Plan &pl, const void *in, int64_t *idx_out, void *v
 
 // Validation: everything that can be said without a device or a pointer.
 int argreduce_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis) {
+    using namespace axis_plan;
     if (kind != SMHIP_ARG_MAX && kind != SMHIP_ARG_MIN) return fail(SMHIP_ERR_INVALID, "%s: bad kind %d", who, kind);
-    if (!valid_dtype(dtype)) return fail(SMHIP_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-    if (ndim < 1 || ndim > SMHIP_MAX_NDIM) return fail(SMHIP_ERR_INVALID, "%s: ndim %d outside 1..%d", who, ndim, SMHIP_MAX_NDIM);
-    if (axis < 0 || axis >= ndim) return fail(SMHIP_ERR_INVALID, "%s: axis %d outside 0..%d", who, axis, ndim - 1);
-    if (!shape || !strides) return fail(SMHIP_ERR_INVALID, "%s: null shape/strides", who);
+    if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
+    if (int rc = check_axis(who, axis, ndim)) return rc;
+    if (int rc = check_extents(who, shape, strides, ndim)) return rc;
     int64_t nout = 1;
-    for (int d = 0; d < ndim; ++d) {
-        if (shape[d] < 0 || strides[d] < 0) return fail(SMHIP_ERR_INVALID, "%s: negative extent or stride at dim %d", who, d);
+    for (int d = 0; d < ndim; ++d)
         if (d != axis) nout *= shape[d];
-    }
     if (nout > 0 && shape[axis] == 0) return fail(SMHIP_ERR_INVALID, "%s: argmax / argmin over an empty extent", who);
     return SMHIP_OK;
 }
@@ -449,18 +402,10 @@ int launch_argreduce_axis(int kind, int dtype, const void *a, const int64_t *sha
     Plan pl;
     make_plan(dtype, shape, strides, ndim, axis, &pl);
     if (pl.route == SMHIP_ARG_ROUTE_NONE) return SMHIP_OK;
-    struct Owned {
-        void *p = nullptr;
-        ~Owned() { if (p) smhip_free(p); }  // stream-ordered pool: safe while the kernels are still queued
-    } copy;
+    axis_plan::Pooled copy;
     const void *in = a;
-    if (pl.copy) {
-        int64_t total = 1, dense[SMHIP_MAX_NDIM];
-        for (int d = ndim - 1; d >= 0; --d) dense[d] = total, total *= shape[d];
-        if (int rc = smhip_alloc(&copy.p, (size_t)total * dtype_size(dtype))) return rc;
-        if (int rc = launch_copy_strided(dtype, a, strides, copy.p, dense, shape, ndim, s)) return rc;
-        in = copy.p;
-    }
+    if (pl.copy)
+        if (int rc = copy.dense_copy(dtype, a, shape, strides, ndim, s, &in)) return rc;
     switch (dtype) {
         case SMHIP_F32: return run_kind<float>(kind, pl, in, index_out, value_out, s);
         case SMHIP_F64: return run_kind<double>(kind, pl, in, index_out, value_out, s);

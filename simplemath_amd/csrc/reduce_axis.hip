@@ -6,9 +6,12 @@
 //   mean   fp64 sum / count, rounded once (integer types: SMHIP_ERR_UNSUPPORTED)
 //   max / min   exact; NaN propagates (which of +-0 a tie returns is not specified)
 //
-// Planner (host only; smhip_reduce_plan reports it).  Size-1 axes are dropped, the rest ordered by stride (largest first) and
-// neighbours that are adjacent in memory -- and, for kept axes, in the result -- merged.  One reduced axis between at most one
-// kept axis outside it and one inside it is the canonical problem
+// Planner (host only; smhip_reduce_plan reports it).  The rules every axis family plans by are written once, in axis_plan.h:
+// the merging of axes, the canonical walk, lanes per short row, the split of R, the capped grid, the argument checks and the
+// pooled dense copy.  What is here is their use, and what only the reductions have: several reduced groups and CHANNEL.
+// Size-1 axes are dropped, the rest ordered by stride (largest first) and neighbours that are adjacent in memory -- and, for
+// kept axes, in the result -- merged.  One reduced axis between at most one kept axis outside it and one inside it is the
+// canonical problem
 //     out[o, i] = reduce_r a[o*so + r*sr + i*si]          (O, R, I)
 // so sum(A.T, 0) is the same walk as sum(A, 1) and a transposed view is never copied.  Anything else:
 //   * several reduced groups (axes 0 and 2 of a 3-D array): one pass per group, innermost first, through a dense
@@ -21,7 +24,7 @@
 //            four vectors per lane in flight.
 //   COLUMN   si = 1.  A lane owns 4 consecutive kept columns and walks R, four rows in flight; lanes are packed over
 //            (o, chunk, column quad), so few columns per outer index do not leave workgroups idle.
-// Every kernel loops over its tasks grid-stride under a capped grid: any O fits HIP's 32-bit work-item count.
+// Every kernel loops over its tasks grid-stride under a capped grid (SMHIP_REDUCE_GRID_CAP): any O fits HIP's 32-bit work-item count.
 //   CHANNEL  si = 1, sr = I <= 8, R >= 1024 (NHWC per-channel: (N,H,W,3) over axes 0-2 is O = 1, R = N*H*W, I = 3): the (R, I) block is
 //            one dense stream; a workgroup step covers 256 * I vectors, a multiple of I elements, so each lane's vector
 //            slots belong to fixed channels -- per-slot accumulators, no divide in the loop, folded into channels at the end.
@@ -44,20 +47,15 @@ namespace smhip {
 namespace {
 
 using namespace dev;
+using namespace axis_plan;  // kBlock, kRowsInFlight, OutMap and the planner's rules
 
-constexpr int kBlock = 256;
 constexpr int kChannelMax = 8;                 // CHANNEL route: at most this many kept columns
 constexpr int64_t kChannelMinR = 4 * kBlock;    // ... and at least one workgroup step of stream (256 * I vectors) per outer
                                                 // index: shorter blocks go to COLUMN, whose lanes pack several (o, c) tasks
-constexpr int64_t kTargetLanes = (int64_t)1 << 18;  // lanes a launch should have before R is split (256 CUs x 1024)
-
-// Where a launch's results go: out[o*oso + i*osi + c*ocs] (c = the chunk of R; 0 when R is not split).
-struct OutMap { int64_t oso, osi, ocs; };
 
 // ---- ROW, short rows: a segment of g lanes per row, every row at most g loads (vectors, then the R % W tail elements one
 // per lane).  A wave covers kRowsInFlight * 64 / g consecutive rows (rows of the outer index, stride so); row = o, or for a
 // finishing launch o * I2 + i (the partials of output (o, i)), written to out[(row / I2)*oso + (row % I2)*osi].
-constexpr int kRowsInFlight = 4;
 template <typename TI, typename TO, int K>
 __global__ __launch_bounds__(kBlock) void row_short_kernel(const TI *__restrict__ a, int64_t rows, int64_t so, int64_t R, int g, int64_t I2,
                                                            TO *__restrict__ out, OutMap om, double divisor, int nt) {
@@ -274,10 +272,8 @@ __global__ __launch_bounds__(kBlock) void channel_kernel(const TI *__restrict__ 
 enum Route { kRouteNone = SMHIP_REDUCE_ROUTE_NONE, kRouteRow = SMHIP_REDUCE_ROUTE_ROW, kRouteColumn = SMHIP_REDUCE_ROUTE_COLUMN,
              kRouteChannel = SMHIP_REDUCE_ROUTE_CHANNEL, kRouteFill = SMHIP_REDUCE_ROUTE_FILL, kRouteGather = SMHIP_REDUCE_ROUTE_GATHER };
 
-struct Pass {
+struct Pass : Canon {
     int route = kRouteNone;
-    int64_t O = 1, R = 1, I = 1, so = 0, sr = 1, si = 1;
-    int64_t oso = 1, osi = 1;  // where result (o, i) goes: out[o*oso + i*osi]
     int64_t C = 1, CL = 0;  // chunks of R (C > 1: a finishing launch) and their length (elements of the row / stream, rows of a column)
     int g = 0;              // ROW: lanes per row (4, 16, 64), 0 = a wave per row
 };
@@ -292,77 +288,40 @@ struct Plan {
     int64_t total_out = 0, total_r = 0;
 };
 
-int vec_width(int dtype) { return dtype == SMHIP_F64 || dtype == SMHIP_I64 ? 2 : 4; }
-
-using axis_plan::Ax;  // axis_plan.h: the merging of axes, shared with argreduce_axis.hip
-using axis_plan::merge_axes;
-using axis_plan::row_major;
-
-// Splits and row segments of one canonical pass; counts its launches.
+// Splits and row segments of one canonical pass; counts its launches.  An unsplit pass walks one chunk of R rounded up to
+// whole steps (ROW, CHANNEL) or of R itself (COLUMN).
 void shape_pass(Pass &p, int dtype, int *launches) {
     const int64_t W = vec_width(dtype);
-    p.C = 1;
+    Split sp{1, 0};
     if (p.route == kRouteRow) {
-        const int64_t nvec = p.R / W, tail = p.R - nvec * W;
-        if (nvec + tail <= 64) {
-            p.g = nvec + tail <= 4 ? 4 : nvec + tail <= 16 ? 16 : 64;
-        } else {
-            p.g = 0;
+        p.g = segment_lanes(row_loads(p.R, W));
+        if (p.g == 0) {
             const int64_t unit = 4 * 64 * W;  // one guard-free step of a wave
-            p.CL = (p.R + unit - 1) / unit * unit;
-            const int64_t lanes = p.O * 64;
-            if (lanes < kTargetLanes) {
-                const int64_t want = std::min((kTargetLanes + lanes - 1) / lanes, (p.R + unit - 1) / unit);
-                if (want > 1) {
-                    const int64_t per = (p.R + want - 1) / want;
-                    p.CL = (per + unit - 1) / unit * unit;
-                    p.C = (p.R + p.CL - 1) / p.CL;
-                }
-            }
+            p.CL = ceil_div(p.R, unit) * unit;
+            sp = split_row(p.O * 64, p.R, unit);
         }
     } else if (p.route == kRouteColumn) {
         p.CL = p.R;
-        const int64_t lanes = p.O * ((p.I + 3) / 4);
-        if (lanes < kTargetLanes) {
-            const int64_t want = std::min((kTargetLanes + lanes - 1) / lanes, (p.R + 15) / 16);
-            if (want > 1) {
-                const int64_t per = (p.R + want - 1) / want;
-                p.CL = (per + 3) / 4 * 4;
-                p.C = (p.R + p.CL - 1) / p.CL;
-            }
-        }
-    } else if (p.route == kRouteChannel) {
+        sp = split_column(p.O * ceil_div(p.I, 4), p.R);
+    } else if (p.route == kRouteChannel) {  // the (R, I) block as one stream of L elements
         const int64_t L = p.R * p.I, step = (int64_t)kBlock * p.I * W;
-        p.CL = (L + step - 1) / step * step;
-        const int64_t lanes = p.O * kBlock;
-        if (lanes < kTargetLanes) {
-            const int64_t want = std::min((kTargetLanes + lanes - 1) / lanes, (L + step - 1) / step);
-            if (want > 1) {
-                const int64_t per = (L + want - 1) / want;
-                p.CL = (per + step - 1) / step * step;
-                p.C = (L + p.CL - 1) / p.CL;
-            }
-        }
+        p.CL = ceil_div(L, step) * step;
+        sp = split_row(p.O * kBlock, L, step);
     }
+    p.C = 1;
+    if (sp.CL) p.C = sp.C, p.CL = sp.CL;
     *launches += p.C > 1 ? 2 : 1;
 }
 
-// Canonical single pass of a merged axis list, if it has one: [kept] reduced [kept] with the route's unit stride.
+// COLUMN's refinement: few kept columns that lie side by side, and at least a workgroup step of stream per outer index.
+bool channel_walk(const Canon &c) { return c.I <= kChannelMax && c.sr == c.I && c.R >= kChannelMinR; }
+
+// Canonical single pass of a merged axis list, if it has one.
 bool single_pass(const Ax *ax, int n, Pass *p) {
-    int red = -1;
-    for (int k = 0; k < n; ++k)
-        if (ax[k].red) {
-            if (red >= 0) return false;
-            red = k;
-        }
-    if (red < 0 || red > 1 || n - red - 1 > 1) return false;
     Pass q;
-    q.R = ax[red].n, q.sr = ax[red].st;
-    if (red == 1) q.O = ax[0].n, q.so = ax[0].st, q.oso = ax[0].ost;
-    if (red + 1 < n) q.I = ax[red + 1].n, q.si = ax[red + 1].st, q.osi = ax[red + 1].ost;
-    if (q.I == 1 && q.sr == 1) q.route = kRouteRow;
-    else if (q.I > 1 && q.si == 1) q.route = q.I <= kChannelMax && q.sr == q.I && q.R >= kChannelMinR ? kRouteChannel : kRouteColumn;
-    else return false;
+    const Walk walk = canonical(ax, n, &q);
+    if (walk == kWalkNone) return false;
+    q.route = walk == kWalkRow ? kRouteRow : channel_walk(q) ? kRouteChannel : kRouteColumn;
     *p = q;
     return true;
 }
@@ -370,12 +329,9 @@ bool single_pass(const Ax *ax, int n, Pass *p) {
 // Validation: everything that can be said without a device.
 int check_args(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t mask) {
     if (kind < SMHIP_REDUCE_SUM || kind > SMHIP_REDUCE_MIN) return fail(SMHIP_ERR_INVALID, "%s: bad kind %d", who, kind);
-    if (!valid_dtype(dtype)) return fail(SMHIP_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-    if (ndim < 1 || ndim > SMHIP_MAX_NDIM) return fail(SMHIP_ERR_INVALID, "%s: ndim %d outside 1..%d", who, ndim, SMHIP_MAX_NDIM);
+    if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
     if (mask == 0 || (mask >> ndim) != 0) return fail(SMHIP_ERR_INVALID, "%s: axes mask 0x%x empty or beyond ndim %d", who, mask, ndim);
-    if (!shape || !strides) return fail(SMHIP_ERR_INVALID, "%s: null shape/strides", who);
-    for (int d = 0; d < ndim; ++d)
-        if (shape[d] < 0 || strides[d] < 0) return fail(SMHIP_ERR_INVALID, "%s: negative extent or stride at dim %d", who, d);
+    if (int rc = check_extents(who, shape, strides, ndim)) return rc;
     if (kind == SMHIP_REDUCE_MEAN && (dtype == SMHIP_I32 || dtype == SMHIP_I64))
         return fail(SMHIP_ERR_UNSUPPORTED, "%s: mean of an integer type", who);
     int64_t nout = 1, nr = 1;
@@ -413,8 +369,7 @@ void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim
         // dense in index order (copied there first unless it already is), one pass per reduced group, innermost first
         pl->copy = zero_stride || !row_major(shape, strides, ndim);
         int64_t dense[SMHIP_MAX_NDIM];
-        int64_t acc = 1;
-        for (int d = ndim - 1; d >= 0; --d) dense[d] = acc, acc *= shape[d];
+        dense_strides(shape, ndim, dense);
         n = merge_axes(shape, dense, ndim, mask, true, ax);
         while (true) {
             int last = -1;
@@ -428,7 +383,7 @@ void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim
             for (int k = 0; k < last; ++k) q.O *= ax[k].n;
             q.sr = q.I, q.si = 1, q.so = q.R * q.I;
             q.oso = q.I, q.osi = 1;  // the pass's result: dense (O, I)
-            q.route = q.I == 1 ? kRouteRow : q.I <= kChannelMax && q.R >= kChannelMinR ? kRouteChannel : kRouteColumn;
+            q.route = q.I == 1 ? kRouteRow : channel_walk(q) ? kRouteChannel : kRouteColumn;
             pl->pass[pl->npasses++] = q;
             // what remains: the axes before it, and the kept one after it merged onto the kept one before it (dense)
             if (last + 1 < n) {
@@ -454,20 +409,7 @@ void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim
 }
 
 // ------------------------------------------------------------------------------------------------------ launching
-// Every kernel loops over its tasks (grid-stride), so the grid can be capped: HIP counts a grid in work-items in 32 bits,
-// and a launch of more than 2^32 / 256 workgroups would fail.  2^20 workgroups (2^28 work-items) is above what any shape of
-// the rate table needs, so the loops run once per lane there.  SMHIP_REDUCE_GRID_CAP=<workgroups> lowers it (the tests run
-// every loop at small sizes with it).
-unsigned grid_cap() {
-    static const int64_t cap = [] {
-        const char *e = getenv("SMHIP_REDUCE_GRID_CAP");
-        const long long v = e && *e ? atoll(e) : 0;
-        return v > 0 && v < ((int64_t)1 << 20) ? (int64_t)v : ((int64_t)1 << 20);
-    }();
-    return (unsigned)cap;
-}
-unsigned capped(int64_t blocks) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, grid_cap())); }
-unsigned blocks_for(int64_t waves) { return capped((waves + kBlock / 64 - 1) / (kBlock / 64)); }
+const GridCap &grid_cap() { static const GridCap g(getenv("SMHIP_REDUCE_GRID_CAP")); return g; }  // the cap of every launch here, read once
 
 // One canonical pass: in (TI) -> out (TO) at `om`, with split and finishing launch as planned.
 template <typename TI, typename TO, typename S, int K>
@@ -487,18 +429,18 @@ int run_pass(const Pass &p, const TI *in, TO *out, OutMap om, double divisor, hi
     auto first = [&](auto *dst, OutMap m, double div) -> int {
         typedef typename std::remove_pointer<decltype(dst)>::type D;
         if (p.route == kRouteRow && p.g > 0) {
-            const int64_t waves = (p.O + kRowsInFlight * (64 / p.g) - 1) / (kRowsInFlight * (64 / p.g));
-            hipLaunchKernelGGL((row_short_kernel<TI, D, K>), dim3(blocks_for(waves)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.g, (int64_t)1, dst, m, div, nt);
+            const int64_t waves = ceil_div(p.O, kRowsInFlight * (64 / p.g));
+            hipLaunchKernelGGL((row_short_kernel<TI, D, K>), dim3(grid_cap().blocks_for(waves)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.g, (int64_t)1, dst, m, div, nt);
         } else if (p.route == kRouteRow) {
-            hipLaunchKernelGGL((row_long_kernel<TI, D, K>), dim3(blocks_for(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.CL, p.C, (int64_t)1, dst, m, div, nt);
+            hipLaunchKernelGGL((row_long_kernel<TI, D, K>), dim3(grid_cap().blocks_for(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.CL, p.C, (int64_t)1, dst, m, div, nt);
         } else if (p.route == kRouteColumn) {
-            const int64_t lanes = p.O * p.C * ((p.I + 3) / 4);
-            hipLaunchKernelGGL((column_kernel<TI, D, K>), dim3(capped((lanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.sr, p.I, p.CL, p.C, dst, m, div, nt);
+            const int64_t lanes = p.O * p.C * ceil_div(p.I, 4);
+            hipLaunchKernelGGL((column_kernel<TI, D, K>), dim3(grid_cap().capped(ceil_div(lanes, kBlock))), dim3(kBlock), 0, s, in, p.O, p.so, p.R, p.sr, p.I, p.CL, p.C, dst, m, div, nt);
         } else {
-            if (p.O * p.C <= (int64_t)grid_cap())
-                hipLaunchKernelGGL((channel_kernel<TI, D, K, false>), dim3(capped(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R * p.I, (int)p.I, p.CL, p.C, dst, m, div, nt);
+            if (p.O * p.C <= (int64_t)grid_cap().cap)
+                hipLaunchKernelGGL((channel_kernel<TI, D, K, false>), dim3(grid_cap().capped(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R * p.I, (int)p.I, p.CL, p.C, dst, m, div, nt);
             else
-                hipLaunchKernelGGL((channel_kernel<TI, D, K, true>), dim3(capped(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R * p.I, (int)p.I, p.CL, p.C, dst, m, div, nt);
+                hipLaunchKernelGGL((channel_kernel<TI, D, K, true>), dim3(grid_cap().capped(p.O * p.C)), dim3(kBlock), 0, s, in, p.O, p.so, p.R * p.I, (int)p.I, p.CL, p.C, dst, m, div, nt);
         }
         SMHIP_LAUNCH_CHECK("reduce_axes");
         return SMHIP_OK;
@@ -506,13 +448,12 @@ int run_pass(const Pass &p, const TI *in, TO *out, OutMap om, double divisor, hi
     if (p.C == 1) return first(out, om, divisor);
     if (int rc = first(part, pm, 0.0)) return rc;
     // finishing: rows (o, i) of C partials each, in index order
-    const int64_t rows = p.O * p.I, W = VecTraits<S>::width, nvec = p.C / W, tail = p.C - nvec * W;
-    if (nvec + tail <= 64) {
-        const int g = nvec + tail <= 4 ? 4 : nvec + tail <= 16 ? 16 : 64;
-        const int64_t waves = (rows + kRowsInFlight * (64 / g) - 1) / (kRowsInFlight * (64 / g));
-        hipLaunchKernelGGL((row_short_kernel<S, TO, K>), dim3(blocks_for(waves)), dim3(kBlock), 0, s, part, rows, p.C, p.C, g, p.I, out, om, divisor, 0);
+    const int64_t rows = p.O * p.I;
+    if (const int g = segment_lanes(row_loads(p.C, VecTraits<S>::width))) {
+        const int64_t waves = ceil_div(rows, kRowsInFlight * (64 / g));
+        hipLaunchKernelGGL((row_short_kernel<S, TO, K>), dim3(grid_cap().blocks_for(waves)), dim3(kBlock), 0, s, part, rows, p.C, p.C, g, p.I, out, om, divisor, 0);
     } else {
-        hipLaunchKernelGGL((row_long_kernel<S, TO, K>), dim3(blocks_for(rows)), dim3(kBlock), 0, s, part, rows, p.C, p.C, p.C, (int64_t)1, p.I, out, om, divisor, 0);
+        hipLaunchKernelGGL((row_long_kernel<S, TO, K>), dim3(grid_cap().blocks_for(rows)), dim3(kBlock), 0, s, part, rows, p.C, p.C, p.C, (int64_t)1, p.I, out, om, divisor, 0);
     }
     SMHIP_LAUNCH_CHECK("reduce_axes finish");
     return SMHIP_OK;
@@ -522,18 +463,11 @@ int run_pass(const Pass &p, const TI *in, TO *out, OutMap om, double divisor, hi
 template <typename T, int K>
 int run_plan(const Plan &pl, int dtype, const T *a, const int64_t *shape, const int64_t *strides, int ndim, T *out, double divisor, hipStream_t s) {
     typedef typename std::conditional<K == kSum && std::is_floating_point<T>::value, double, T>::type S;
-    struct Owned {
-        void *p = nullptr;
-        ~Owned() { if (p) smhip_free(p); }
-    } copy, tmp[2];
-    const T *in = a;
-    if (pl.copy) {
-        int64_t total = 1, dense[SMHIP_MAX_NDIM];
-        for (int d = ndim - 1; d >= 0; --d) dense[d] = total, total *= shape[d];
-        if (int rc = smhip_alloc(&copy.p, (size_t)total * sizeof(T))) return rc;
-        if (int rc = launch_copy_strided(dtype, a, strides, copy.p, dense, shape, ndim, s)) return rc;
-        in = static_cast<const T *>(copy.p);
-    }
+    Pooled copy, tmp[2];
+    const void *dense = a;
+    if (pl.copy)
+        if (int rc = copy.dense_copy(dtype, a, shape, strides, ndim, s, &dense)) return rc;
+    const T *in = static_cast<const T *>(dense);
     const int np = pl.npasses;
     if (np == 1) {
         const Pass &p = pl.pass[0];
@@ -545,10 +479,9 @@ int run_plan(const Plan &pl, int dtype, const T *a, const int64_t *shape, const 
         const Pass &p = pl.pass[k];
         const OutMap om{p.oso, p.osi, 0};
         if (k == np - 1) return run_pass<S, T, S, K>(p, prev, out, om, divisor, s);
-        Owned &buf = tmp[k & 1];
-        if (buf.p) smhip_free(buf.p), buf.p = nullptr;  // stream-ordered pool: the pass two back has been queued before
-        if (int rc = smhip_alloc(&buf.p, (size_t)(p.O * p.I) * sizeof(S))) return rc;
-        S *dst = static_cast<S *>(buf.p);
+        void *buf;  // the pass two back, whose result this owner hands back first, has been queued before
+        if (int rc = tmp[k & 1].take((size_t)(p.O * p.I) * sizeof(S), &buf)) return rc;
+        S *dst = static_cast<S *>(buf);
         int rc = k == 0 ? run_pass<T, S, S, K>(p, in, dst, om, 0.0, s) : run_pass<S, S, S, K>(p, prev, dst, om, 0.0, s);
         if (rc) return rc;
         prev = dst;
@@ -593,11 +526,8 @@ int launch_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape,
         return launch_fill(dtype, out, &zero, (size_t)pl.total_out, s);
     }
     if (pl.route_code == kRouteGather) {
-        int64_t ost[SMHIP_MAX_NDIM], acc = 1;
-        for (int d = ndim - 1; d >= 0; --d) {
-            ost[d] = 0;
-            if (!(axes_mask >> d & 1)) ost[d] = acc, acc *= shape[d];
-        }
+        int64_t ost[SMHIP_MAX_NDIM];
+        axis_plan::dense_strides(shape, ndim, ost, ~axes_mask);
         return launch_copy_strided(dtype, a, strides, out, ost, shape, ndim, s);
     }
     switch (dtype) {

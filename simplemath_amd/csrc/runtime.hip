@@ -760,6 +760,11 @@ size_t span_bytes(const int64_t *shape, const int64_t *strides, int ndim, size_t
         if (shape[i] > 0) last += (size_t)(shape[i] - 1) * (size_t)strides[i];
     return (last + 1) * esz;
 }
+// Do two byte spans share a byte?  (An empty span shares none.)
+bool spans_overlap(Span x, Span y) {
+    const char *x0 = static_cast<const char *>(x.p), *y0 = static_cast<const char *>(y.p);
+    return x.bytes && y.bytes && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
+}
 }  // namespace
 
 extern "C" {
@@ -1471,8 +1476,7 @@ int smhip_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, co
     if (!a || !out) return fail(SMHIP_ERR_INVALID, "scan_axis: null buffer");
     if (!(out == a && dense)) {  // in place is the one overlap a scan can take: a lane stores only what it has loaded itself
         const size_t esz = dtype_size(dtype);
-        const char *a0 = static_cast<const char *>(a), *o0 = static_cast<const char *>(out);
-        if (a0 < o0 + (size_t)n * esz && o0 < a0 + span_bytes(shape, strides, ndim, esz))
+        if (spans_overlap(Span{a, span_bytes(shape, strides, ndim, esz)}, Span{out, (size_t)n * esz}))
             return fail(SMHIP_ERR_INVALID, "scan_axis: the result overlaps the operand (only out == a with a dense operand is allowed)");
     }
     SMHIP_ACQUIRE(s);  // undeclared spans (a pooled copy, the chunks' totals): ordered behind everything, recorded tiny operators flushed first
@@ -1496,11 +1500,7 @@ int smhip_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shap
     if (!a || !index_out) return fail(SMHIP_ERR_INVALID, "argreduce_axis: null buffer");
     const size_t esz = dtype_size(dtype);
     const Span sa{a, span_bytes(shape, strides, ndim, esz)}, si{index_out, (size_t)nout * sizeof(int64_t)}, sv{value_out, value_out ? (size_t)nout * esz : 0};
-    auto overlap = [](Span x, Span y) {
-        const char *x0 = static_cast<const char *>(x.p), *y0 = static_cast<const char *>(y.p);
-        return x.bytes && y.bytes && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
-    };
-    if (overlap(si, sa) || overlap(sv, sa) || overlap(si, sv))
+    if (spans_overlap(si, sa) || spans_overlap(sv, sa) || spans_overlap(si, sv))
         return fail(SMHIP_ERR_INVALID, "argreduce_axis: index_out / value_out overlap the operand or each other");
     // the operand's span and the index result are declared; the call still orders itself behind everything and everything
     // later behind it (a pooled copy, the chunks' pairs and value_out are not declared), recorded tiny operators flushed first

@@ -8,7 +8,8 @@
 // is the canonical problem
 //     out[o, r, i] = scan_r a[o, r, i]          (O, R, I) = (extents before the axis, the axis, extents after it)
 // with both sides dense in that order.  Any other operand (a transposed or stepped view, a stride-0 axis, a sub-block) is
-// copied dense first (smhip_copy_strided's kernels, a pooled temporary): there are no transposing scan kernels.
+// copied dense first (smhip_copy_strided's kernels, a pooled temporary): there are no transposing scan kernels.  Lanes per
+// short row, the capped grid, the argument checks and that copy are axis_plan.h's; when R is split is the scans' own rule.
 // Routes:
 //   COPYONLY  R = 1: the result is the operand.
 //   ROW       I = 1.  Rows of at most 64 loads (16-byte vectors, then the R % W tail elements one per lane): a SEGMENT of
@@ -33,6 +34,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "axis_plan.h"
 #include "fold.hip.h"
 #include "internal.h"
 #include "ops.hip.h"
@@ -42,11 +44,10 @@ namespace smhip {
 namespace {
 
 using namespace dev;
+using namespace axis_plan;  // kBlock, kRowsInFlight, kTargetLanes and the planner's shared rules
 
-constexpr int kBlock = 256, kWaves = kBlock / 64;
+constexpr int kWaves = kBlock / 64;
 constexpr int kTileVecs = 4;      // ROW, long rows: vectors per lane and tile
-constexpr int kRowsInFlight = 4;  // ROW, short rows: rows per segment
-constexpr int64_t kTargetLanes = (int64_t)1 << 18;  // lanes a split launch aims for (256 CUs x 1024), as the reductions do
 // When R is split.  The split reads the operand twice (3 x sizeof(T) per element instead of 2), so it is taken only where
 // the one-launch walk would leave most of the machine idle: ROW with fewer than 1024 rows (a workgroup each), COLUMN with
 // fewer than 64 workgroups (a quarter of the CUs).  A split COLUMN launch aims at 1024 workgroups.
@@ -346,34 +347,26 @@ struct Plan {
     int code() const { return route | (C > 1 ? SMHIP_SCAN_SPLIT : 0) | (copy ? SMHIP_SCAN_COPY : 0); }
 };
 
-int vec_width(int dtype) { return dtype == SMHIP_F64 || dtype == SMHIP_I64 ? 2 : 4; }
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, Plan *pl) {
     *pl = Plan();
-    int64_t O = 1, I = 1, dense = 1;
-    bool row_major = true;
-    for (int d = ndim - 1; d >= 0; --d) {
-        if (shape[d] != 1 && strides[d] != dense) row_major = false;
-        dense *= shape[d];
+    int64_t O = 1, I = 1;
+    for (int d = 0; d < ndim; ++d) {
         if (d < axis) O *= shape[d];
         if (d > axis) I *= shape[d];
     }
     const int64_t R = shape[axis];
     pl->O = O, pl->R = R, pl->I = I, pl->CL = R;
-    if (dense == 0) return;
+    if (O * R * I == 0) return;
     if (R == 1) {
         pl->route = SMHIP_SCAN_ROUTE_COPYONLY, pl->launches = 1;
         return;
     }
-    pl->copy = !row_major;
+    pl->copy = !row_major(shape, strides, ndim);
     const int64_t W = vec_width(dtype);
     if (I == 1) {
         pl->route = SMHIP_SCAN_ROUTE_ROW;
-        const int64_t loads = R / W + R % W;
-        if (loads <= 64) {
-            pl->g = loads <= 4 ? 4 : loads <= 16 ? 16 : 64;
-        } else if (O < kRowSplitBelowRows) {
+        pl->g = segment_lanes(row_loads(R, W));
+        if (pl->g == 0 && O < kRowSplitBelowRows) {
             const int64_t tile = (int64_t)kBlock * kTileVecs * W;
             const int64_t want = std::min({ceil_div(kRowSplitBelowRows, O), R / tile, kRowMaxChunks});  // a chunk: at least a tile
             if (want > 1) {
@@ -397,17 +390,7 @@ void make_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim
 }
 
 // ------------------------------------------------------------------------------------------------------ launching
-// As the reductions: every kernel loops over its tasks, so the grid can be capped below HIP's 32-bit work-item count.
-// SMHIP_SCAN_GRID_CAP=<workgroups> lowers the cap (the tests run every loop at small sizes with it).
-unsigned grid_cap() {
-    static const int64_t cap = [] {
-        const char *e = getenv("SMHIP_SCAN_GRID_CAP");
-        const long long v = e && *e ? atoll(e) : 0;
-        return v > 0 && v < ((int64_t)1 << 20) ? (int64_t)v : ((int64_t)1 << 20);
-    }();
-    return (unsigned)cap;
-}
-unsigned capped(int64_t blocks) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, grid_cap())); }
+const GridCap &grid_cap() { static const GridCap g(getenv("SMHIP_SCAN_GRID_CAP")); return g; }  // the cap of every launch here, read once
 
 template <typename T, int K>
 int run_scan(const Plan &pl, const T *in, T *out, hipStream_t s) {
@@ -423,16 +406,16 @@ int run_scan(const Plan &pl, const T *in, T *out, hipStream_t s) {
     }
     if (pl.route == SMHIP_SCAN_ROUTE_ROW && pl.g > 0) {
         const int64_t per_wave = kRowsInFlight * (64 / pl.g), waves = ceil_div(pl.O, per_wave);
-        hipLaunchKernelGGL((row_short_kernel<T, K>), dim3(capped(ceil_div(waves, kWaves))), dim3(kBlock), 0, s, in, out, pl.O, pl.R, pl.g, pol);
+        hipLaunchKernelGGL((row_short_kernel<T, K>), dim3(grid_cap().blocks_for(waves)), dim3(kBlock), 0, s, in, out, pl.O, pl.R, pl.g, pol);
     } else if (pl.route == SMHIP_SCAN_ROUTE_ROW) {
-        const dim3 grid(capped(pl.O * pl.C));
+        const dim3 grid(grid_cap().capped(pl.O * pl.C));
         if (pl.C > 1) {
             hipLaunchKernelGGL((row_long_kernel<T, K, true>), grid, dim3(kBlock), 0, s, in, out, pl.O, pl.R, pl.CL, pl.C, part, pol);
             SMHIP_LAUNCH_CHECK("scan_axis totals");
         }
         hipLaunchKernelGGL((row_long_kernel<T, K, false>), grid, dim3(kBlock), 0, s, in, out, pl.O, pl.R, pl.CL, pl.C, part, pol);
     } else {
-        const dim3 grid(capped(pl.O * pl.C * ceil_div(pl.I, kColStrip)));
+        const dim3 grid(grid_cap().capped(pl.O * pl.C * ceil_div(pl.I, kColStrip)));
         if (pl.C > 1) {
             hipLaunchKernelGGL((column_kernel<T, K, true>), grid, dim3(kBlock), 0, s, in, out, pl.O, pl.R, pl.I, pl.CL, pl.C, part, pol);
             SMHIP_LAUNCH_CHECK("scan_axis totals");
@@ -460,14 +443,11 @@ int run_kind(int kind, const Plan &pl, const void *in, void *out, hipStream_t s)
 
 // Validation: everything that can be said without a device.
 int scan_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis) {
+    using namespace axis_plan;
     if (kind < SMHIP_SCAN_SUM || kind > SMHIP_SCAN_MIN) return fail(SMHIP_ERR_INVALID, "%s: bad kind %d", who, kind);
-    if (!valid_dtype(dtype)) return fail(SMHIP_ERR_INVALID, "%s: bad dtype %d", who, dtype);
-    if (ndim < 1 || ndim > SMHIP_MAX_NDIM) return fail(SMHIP_ERR_INVALID, "%s: ndim %d outside 1..%d", who, ndim, SMHIP_MAX_NDIM);
-    if (axis < 0 || axis >= ndim) return fail(SMHIP_ERR_INVALID, "%s: axis %d outside 0..%d", who, axis, ndim - 1);
-    if (!shape || !strides) return fail(SMHIP_ERR_INVALID, "%s: null shape/strides", who);
-    for (int d = 0; d < ndim; ++d)
-        if (shape[d] < 0 || strides[d] < 0) return fail(SMHIP_ERR_INVALID, "%s: negative extent or stride at dim %d", who, d);
-    return SMHIP_OK;
+    if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
+    if (int rc = check_axis(who, axis, ndim)) return rc;
+    return check_extents(who, shape, strides, ndim);
 }
 
 void scan_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
@@ -485,19 +465,15 @@ int launch_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, c
     Plan pl;
     make_plan(dtype, shape, strides, ndim, axis, &pl);
     if (pl.route == SMHIP_SCAN_ROUTE_NONE) return SMHIP_OK;
-    int64_t total = 1, dense[SMHIP_MAX_NDIM];
-    for (int d = ndim - 1; d >= 0; --d) dense[d] = total, total *= shape[d];
-    if (pl.route == SMHIP_SCAN_ROUTE_COPYONLY) return a == out ? SMHIP_OK : launch_copy_strided(dtype, a, strides, out, dense, shape, ndim, s);
-    struct Owned {
-        void *p = nullptr;
-        ~Owned() { if (p) smhip_free(p); }  // stream-ordered pool: safe while the kernels are still queued
-    } copy;
-    const void *in = a;
-    if (pl.copy) {
-        if (int rc = smhip_alloc(&copy.p, (size_t)total * dtype_size(dtype))) return rc;
-        if (int rc = launch_copy_strided(dtype, a, strides, copy.p, dense, shape, ndim, s)) return rc;
-        in = copy.p;
+    if (pl.route == SMHIP_SCAN_ROUTE_COPYONLY) {
+        int64_t dense[SMHIP_MAX_NDIM];
+        axis_plan::dense_strides(shape, ndim, dense);
+        return a == out ? SMHIP_OK : launch_copy_strided(dtype, a, strides, out, dense, shape, ndim, s);
     }
+    axis_plan::Pooled copy;
+    const void *in = a;
+    if (pl.copy)
+        if (int rc = copy.dense_copy(dtype, a, shape, strides, ndim, s, &in)) return rc;
     switch (dtype) {
         case SMHIP_F32: return run_kind<float>(kind, pl, in, out, s);
         case SMHIP_F64: return run_kind<double>(kind, pl, in, out, s);
