@@ -92,6 +92,7 @@ struct FusionStats {
     unsigned long long reductions = 0;          // axis reductions (smhip_reduce_axes: sum / mean / max / min along axes)
     unsigned long long scans = 0;               // cumulative scans (smhip_scan_axis: cumsum / cumprod / cummax / cummin)
     unsigned long long arg_reductions = 0;      // smhip_argreduce_axis calls: argmax / argmin / max_with_index / min_with_index
+    unsigned long long sorts = 0;               // smhip_sort_axis calls: sort / argsort / sort_with_index and their _flat forms
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -757,6 +758,43 @@ public:
     std::pair<SMArray, SMArray<std::int64_t>> max_with_index(int axis, bool keepdims = false) const { return arg_with_value(SMHIP_ARG_MAX, axis, keepdims); }
     std::pair<SMArray, SMArray<std::int64_t>> min_with_index(int axis, bool keepdims = false) const { return arg_with_value(SMHIP_ARG_MIN, axis, keepdims); }
 
+    // The ORDER along an axis (np.sort / np.argsort with kind="stable"): sort gives the elements of each line in order, argsort
+    // their positions along `axis` as std::int64_t; both have this array's shape and are resident on the device.  Ascending puts
+    // the smaller values first and NaNs last (-0 == +0, all NaNs tie); descending = true puts NaNs, then the larger values first.
+    // In both orders tied elements keep the order of their positions, so descending is not the ascending result reversed: its
+    // first element is where argmax points.  The sorted values are the operand's own bits (which zero, which NaN).  `axis`
+    // counts from the end when negative and is the last one by default; an axis out of range throws std::runtime_error.
+    // sort_flat / argsort_flat sort the row-major flattening, shape {totalSize}.  A pending operator chain as the operand is
+    // evaluated first; each is ONE smhip_sort_axis call (counted in sm::fusion_stats().sorts), sort_with_index giving {values,
+    // positions} from the same call.  The result feeds the next chain or a slice like any array: `x.sort(-1)(SLICE_ALL,
+    // SLICE(0, 5))` is a view of the five smallest of each row.
+    SMArray sort(int axis = -1, bool descending = false) const {
+        SMArray values = device_empty(std::vector<std::size_t>(_shape));
+        sort_along(axis, descending, &values, nullptr);
+        return values;
+    }
+    SMArray<std::int64_t> argsort(int axis = -1, bool descending = false) const {
+        SMArray<std::int64_t> where = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>(_shape));
+        sort_along(axis, descending, nullptr, &where);
+        return where;
+    }
+    std::pair<SMArray, SMArray<std::int64_t>> sort_with_index(int axis = -1, bool descending = false) const {
+        SMArray values = device_empty(std::vector<std::size_t>(_shape));
+        SMArray<std::int64_t> where = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>(_shape));
+        sort_along(axis, descending, &values, &where);
+        return {std::move(values), std::move(where)};
+    }
+    SMArray sort_flat(bool descending = false) const {
+        SMArray values = device_empty(std::vector<std::size_t>{totalSize});
+        sort_all(descending, &values, nullptr);
+        return values;
+    }
+    SMArray<std::int64_t> argsort_flat(bool descending = false) const {
+        SMArray<std::int64_t> where = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{totalSize});
+        sort_all(descending, nullptr, &where);
+        return where;
+    }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -1068,6 +1106,29 @@ private:
         hip::check(smhip_argreduce_axis(kind, hip::dtype_of<T>::id, in, &n, &one, 1, 0, out.device_data_mut(), nullptr));
         ++detail::tls_fusion_stats.arg_reductions;
         return out;
+    }
+
+    // `values` / `where`: dense arrays of this array's shape for the sorted elements / their positions; either may be nullptr.
+    void sort_along(int axis, bool descending, SMArray *values, SMArray<std::int64_t> *where) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "sort / argsort: f32, f64, i32 and i64");
+        const int a = arg_axis(axis);
+        hip::DeviceGuard on(device());
+        const T *in = device_data();  // a pending chain that produces this operand runs here
+        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
+        hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, sh.data(), st.data(),
+                                   static_cast<int>(sh.size()), a, values ? values->device_data_mut() : nullptr, where ? where->device_data_mut() : nullptr));
+        ++detail::tls_fusion_stats.sorts;
+    }
+    // The elements in row-major order as one line: a view is made dense first.
+    void sort_all(bool descending, SMArray *values, SMArray<std::int64_t> *where) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "sort / argsort: f32, f64, i32 and i64");
+        hip::DeviceGuard on(device());
+        std::unique_ptr<SMArray> holder;
+        const T *in = dense_device(holder);
+        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
+        hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, &n, &one, 1, 0,
+                                   values ? values->device_data_mut() : nullptr, where ? where->device_data_mut() : nullptr));
+        ++detail::tls_fusion_stats.sorts;
     }
 
     // Device pointer to a dense version of this array (itself when already dense).

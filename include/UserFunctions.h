@@ -262,6 +262,22 @@ std::pair<SMArray<T>, SMArray<std::int64_t>> max_with_index(const SMArray<T> &ar
 template <typename T>
 std::pair<SMArray<T>, SMArray<std::int64_t>> min_with_index(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.min_with_index(axis, keepdims); }
 
+// The order along an axis (np.sort / np.argsort with kind="stable"): the elements of each line in order, or their positions as
+// SMArray<std::int64_t>; both of `arr`'s shape.  `axis` counts from the end when negative and is the last one when absent;
+// descending puts NaNs, then the larger values first, ties still in the order of their positions.  sort_with_index returns
+// {values, positions} from ONE call; sort_flat / argsort_flat sort the row-major flattening, shape {size}.  Semantics as
+// SMArray::sort(axis) (SMArray.h) and smhip_sort_axis (smhip.h).
+template <typename T>
+SMArray<T> sort(const SMArray<T> &arr, int axis = -1, bool descending = false) { return arr.sort(axis, descending); }
+template <typename T>
+SMArray<std::int64_t> argsort(const SMArray<T> &arr, int axis = -1, bool descending = false) { return arr.argsort(axis, descending); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> sort_with_index(const SMArray<T> &arr, int axis = -1, bool descending = false) { return arr.sort_with_index(axis, descending); }
+template <typename T>
+SMArray<T> sort_flat(const SMArray<T> &arr, bool descending = false) { return arr.sort_flat(descending); }
+template <typename T>
+SMArray<std::int64_t> argsort_flat(const SMArray<T> &arr, bool descending = false) { return arr.argsort_flat(descending); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

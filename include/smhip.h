@@ -391,6 +391,47 @@ int smhip_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shap
 int smhip_argreduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
                          int *route, int *launches, int64_t *ori3, int64_t *chunk);
 
+/* ------------------------------------------------------- sort / argsort */
+/* np.sort / np.argsort with kind="stable" along ONE axis: each line a[o, :, i] is sorted as (element, position) pairs, and the
+ * call returns the elements in that order, their positions, or both.  The contract:
+ *   order        ASCENDING                                              DESCENDING
+ *   numbers      the smaller value first; -0.0 == +0.0                  the larger value first; -0.0 == +0.0
+ *   NaN          after every number, whatever its sign or payload;      before every number; all NaNs tie
+ *                all NaNs tie
+ *   ties         equal values, and NaNs among themselves, keep the order of their positions -- in BOTH orders
+ *   numpy        np.sort(x, axis, kind="stable") and                    NOT the ascending result reversed (ties would run
+ *                np.argsort(x, axis, kind="stable")                     backwards): R - 1 - argsort(flip(x, axis), axis,
+ *                                                                       kind="stable"), flipped along the axis
+ * DESCENDING is the order whose first element is what smhip_argreduce_axis(ARG_MAX) returns, NaN included.  The pairs of a
+ * line are totally ordered, so the result is unique: bit-exact and the same on every run and stream, whatever the tiling.
+ * values_out receives exactly a[..., index, ...], the bits of the operand's elements (which zero, which NaN payload);
+ * index_out the positions along the axis, in [0, shape[axis]), as int64_t. */
+typedef enum smhip_sort_order { SMHIP_SORT_ASCENDING = 0, SMHIP_SORT_DESCENDING = 1 } smhip_sort_order;
+/* `a` is any view (strides in ELEMENTS, >= 0, 0 allowed; rank 1 .. SMHIP_MAX_NDIM; f32, f64, i32 or i64).  Both outputs are
+ * dense row-major over `shape`; either may be NULL, not both.  Arguments are checked before any device is touched
+ * (SMHIP_ERR_INVALID): order, dtype, ndim, axis outside [0, ndim) (not counted from the end), negative extents or strides,
+ * null a / shape / strides, both outputs null, the outputs overlapping each other, an output overlapping a's span.  One overlap
+ * is allowed: values_out == a with `a` dense row-major sorts in place.  shape[axis] >= 2^31 is SMHIP_ERR_UNSUPPORTED (positions
+ * travel as 32 bits inside the kernels).  Any extent of 0, the axis included, is a no-op, whatever the pointers;
+ * shape[axis] == 1 copies the values and writes zeros.  Asynchronous, stream-ordered; recorded tiny operators are flushed first. */
+int smhip_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                    void *values_out_or_null, int64_t *index_out_or_null);
+/* Host only, no device touched: the route smhip_sort_axis would take.  *route = a kernel id (SMHIP_SORT_ROUTE_*) ORed with the
+ * flags below; *launches = the kernel launches of a call that asks for both outputs, not in place; ori3 = {O, R, I}: R is
+ * exactly shape[axis], and O lines of R are sorted with I = 1 when the view is read in place, else O and I are the extents
+ * before and after the axis; *chunk = K, the length of the tiles a line is cut into for the sort in LDS (4096 for every
+ * element type), or R when the line fits one tile.  Any output may be NULL.  The planner's test hook. */
+#define SMHIP_SORT_ROUTE_NONE 0      /* an extent is 0: nothing to compute */
+#define SMHIP_SORT_ROUTE_COPYONLY 1  /* R = 1: the dense copy of a (nothing when in place) and zeros for the positions */
+#define SMHIP_SORT_ROUTE_ROW 2       /* lines of R contiguous elements, each sorted in LDS by a bitonic network on (element, position) pairs */
+#define SMHIP_SORT_MERGE 0x100       /* R > K: launch 1 sorts tiles of K into pooled pairs; ceil(log2(tiles)) merge-path passes between
+                                        two pooled buffers follow, the last one writing the results */
+#define SMHIP_SORT_COPY 0x200        /* staging: the operand is copied so that the sort axis is the unit-stride one (a stepped or
+                                        broadcast view, an axis that is not the innermost in memory), and / or the sorted rows are
+                                        scattered back to the dense row-major results (one launch per output) */
+int smhip_sort_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                    int *route, int *launches, int64_t *ori3, int64_t *chunk);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

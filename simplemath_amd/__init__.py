@@ -48,6 +48,10 @@ ARG_KINDS = {"argmax": ARG_MAX, "argmin": ARG_MIN}
 # smhip_argreduce_plan's route word: a kernel id in the low byte, flags above it
 ARG_ROUTE_NONE, ARG_ROUTE_ROW, ARG_ROUTE_COLUMN = range(3)
 ARG_SPLIT, ARG_COPY = 0x100, 0x200
+SORT_ASCENDING, SORT_DESCENDING = range(2)  # smhip_sort_order
+# smhip_sort_plan's route word: a kernel id in the low byte, flags above it
+SORT_ROUTE_NONE, SORT_ROUTE_COPYONLY, SORT_ROUTE_ROW = range(3)
+SORT_MERGE, SORT_COPY = 0x100, 0x200
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -656,6 +660,73 @@ class Smhip:
         route, launches, ori, chunk = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), C.c_int64(0)
         self._ck(self.c.smhip_argreduce_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)),
                                              C.byref(route), C.byref(launches), ori, C.byref(chunk)))
+        return route.value, launches.value, tuple(int(x) for x in ori), chunk.value
+
+    def sort(self, a: DeviceArray, axis=-1, descending=False, indices=False, out: DeviceArray | None = None):
+        """np.sort(a, axis, kind="stable") of `a` (any view) -> a new dense DeviceArray of a's shape, or into `out`, which must be a
+        dense array of a's dtype and element count (its shape is not changed); `out` may be `a` itself when `a` is dense (in
+        place).  descending=True puts NaNs, then the larger values first, ties still in the order of their positions (not the
+        ascending result reversed).  indices=True returns (values, indices) from the same call, the int64 positions along the
+        axis that np.argsort(kind="stable") gives.  axis=None sorts the row-major flattening and gives shape (a.size,)."""
+        return self._sort(a, axis, descending, True, indices, out, None)
+
+    def argsort(self, a: DeviceArray, axis=-1, descending=False, out: DeviceArray | None = None):
+        """np.argsort(a, axis, kind="stable") -> a new dense int64 DeviceArray of a's shape (or into `out`, a dense int64 array
+        with as many elements): the positions along the axis in sorted order; `descending` and axis=None as in sort()."""
+        return self._sort(a, axis, descending, False, True, None, out)
+
+    def _sort(self, a, axis, descending, want_values, want_indices, out, index_out):
+        if a.dtype not in DTYPES:
+            raise ValueError(f"sort: dtype {a.dtype} (f32, f64, i32 and i64 only)")
+        if axis is None:
+            if not a.is_dense():  # the row-major order of a view: its dense copy
+                if out is a:
+                    raise ValueError("sort: out=a (in place) needs a dense array")
+                dense = self.empty(a.shape, a.dtype)
+                self.assign(dense, a)
+                a = dense
+            shape, strides, axis, result_shape = (a.size,), (1,), 0, (a.size,)
+        else:
+            (axis,) = self._axes(a.ndim, int(axis))
+            shape, strides, result_shape = a.shape, a.strides, a.shape
+        vals = idx = None
+        if want_values:
+            if out is None:
+                vals = self.empty(result_shape, a.dtype)
+            elif out is a and not a.is_dense():
+                raise ValueError("sort: out=a (in place) needs a dense array")
+            elif out.dtype != a.dtype or out.size != a.size or not out.is_dense():
+                raise ValueError(f"sort: out must be a dense {a.dtype} array of {a.size} elements (shape {tuple(result_shape)}); "
+                                 f"got {out.dtype} {out.shape} dense={out.is_dense()}")
+            else:
+                vals = out
+        if want_indices:
+            if index_out is None:
+                idx = self.empty(result_shape, np.int64)
+            elif index_out.dtype != np.dtype(np.int64) or index_out.size != a.size or not index_out.is_dense():
+                raise ValueError(f"argsort: out must be a dense int64 array of {a.size} elements (shape {tuple(result_shape)}); "
+                                 f"got {index_out.dtype} {index_out.shape} dense={index_out.is_dense()}")
+            else:
+                idx = index_out
+        self._ck(self.c.smhip_sort_axis(C.c_int(SORT_DESCENDING if descending else SORT_ASCENDING), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr),
+                                        _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(axis),
+                                        C.c_void_p(vals.ptr if vals is not None else 0), C.c_void_p(idx.ptr if idx is not None else 0)))
+        return (vals, idx) if want_values and want_indices else vals if want_values else idx
+
+    def sort_raw(self, order, dtype, a_ptr, shape, strides, axis, values_ptr=0, index_ptr=0, ndim=None):
+        """smhip_sort_axis with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        return self.c.smhip_sort_axis(C.c_int(order), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                      _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_int(axis),
+                                      C.c_void_p(values_ptr), C.c_void_p(index_ptr))
+
+    def sort_plan(self, dtype, shape, strides, axis, descending=False):
+        """smhip_sort_plan (host only): (route word, launches, (O, R, I), K or R) for a call on shape / strides (elements)."""
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        route, launches, ori, chunk = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), C.c_int64(0)
+        self._ck(self.c.smhip_sort_plan(C.c_int(SORT_DESCENDING if descending else SORT_ASCENDING), C.c_int(dtype), _i64(shape), _i64(strides),
+                                        C.c_int(len(shape)), C.c_int(int(axis)), C.byref(route), C.byref(launches), ori, C.byref(chunk)))
         return route.value, launches.value, tuple(int(x) for x in ori), chunk.value
 
     def sum(self, a: DeviceArray):

@@ -236,4 +236,11 @@ void argreduce_axis_plan(int dtype, const int64_t *shape, const int64_t *strides
 int launch_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis,
                           int64_t *index_out, void *value_out, hipStream_t s);
 
+// sort_axis.hip: stable sort / argsort along an axis (smhip_sort_axis); the checks and the planner are host-only
+int sort_axis_check(const char *who, int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis);
+void sort_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
+                    int64_t *chunk);
+int launch_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *values_out,
+                     int64_t *index_out, hipStream_t s);
+
 }  // namespace smhip

@@ -1517,6 +1517,36 @@ int smhip_argreduce_plan(int kind, int dtype, const int64_t *shape, const int64_
     return SMHIP_OK;
 }
 
+int smhip_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *values_out,
+                    int64_t *index_out) {
+    if (int rc = sort_axis_check("sort_axis", order, dtype, shape, strides, ndim, axis)) return rc;
+    int64_t n = 1;
+    bool dense = true;
+    for (int d = ndim - 1; d >= 0; --d) {
+        if (shape[d] != 1 && strides[d] != n) dense = false;
+        n *= shape[d];
+    }
+    if (n == 0) return SMHIP_OK;
+    if (!a) return fail(SMHIP_ERR_INVALID, "sort_axis: null operand");
+    if (!values_out && !index_out) return fail(SMHIP_ERR_INVALID, "sort_axis: neither values_out nor index_out is given");
+    const size_t esz = dtype_size(dtype);
+    const Span sa{a, span_bytes(shape, strides, ndim, esz)}, sv{values_out, values_out ? (size_t)n * esz : 0},
+        si{index_out, index_out ? (size_t)n * sizeof(int64_t) : 0};
+    // in place is the one overlap a sort can take: the operand is read whole (a line, or launch 1 of a merge) before a result is written
+    if (!(values_out == a && dense) && spans_overlap(sv, sa))
+        return fail(SMHIP_ERR_INVALID, "sort_axis: values_out overlaps the operand (only values_out == a with a dense operand is allowed)");
+    if (spans_overlap(si, sa) || spans_overlap(si, sv)) return fail(SMHIP_ERR_INVALID, "sort_axis: index_out overlaps the operand or values_out");
+    SMHIP_ACQUIRE(s);  // undeclared spans (pooled staging, the merge's pairs): ordered behind everything, recorded tiny operators flushed first
+    return launch_sort_axis(order, dtype, a, shape, strides, ndim, axis, values_out, index_out, s);
+}
+
+int smhip_sort_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
+                    int64_t *chunk) {
+    if (int rc = sort_axis_check("sort_plan", order, dtype, shape, strides, ndim, axis)) return rc;
+    sort_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
+    return SMHIP_OK;
+}
+
 int smhip_sum(int dtype, const void *a, size_t n, double *out_host) {
     if (!out_host) return fail(SMHIP_ERR_INVALID, "sum: null result");
     void *h = nullptr, *d = nullptr;
