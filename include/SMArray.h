@@ -58,6 +58,13 @@ concept ArithmeticOrComplex =
 template <ArithmeticOrComplex T>
 class SMArray;
 
+// What take / take_along_axis do with an index outside [-R, R) of an axis of R elements (smhip.h: smhip_index_mode).
+enum class index_mode {
+    checked = SMHIP_INDEX_CHECKED,  // numpy's rule: negatives count from the end, anything else out of range throws std::out_of_range
+    clip = SMHIP_INDEX_CLIP,        // clamp to [0, R - 1] (np.take(mode="clip")): fully asynchronous
+    wrap = SMHIP_INDEX_WRAP,        // the non-negative remainder mod R (np.take(mode="wrap")): fully asynchronous
+};
+
 namespace detail {
 
 // ---- deferred operator chains ------------------------------------------------------------------------------------------
@@ -93,6 +100,7 @@ struct FusionStats {
     unsigned long long scans = 0;               // cumulative scans (smhip_scan_axis: cumsum / cumprod / cummax / cummin)
     unsigned long long arg_reductions = 0;      // smhip_argreduce_axis calls: argmax / argmin / max_with_index / min_with_index
     unsigned long long sorts = 0;               // smhip_sort_axis calls: sort / argsort / sort_with_index and their _flat forms
+    unsigned long long takes = 0;               // smhip_take_axis calls: take / take_along_axis / take_flat
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -795,6 +803,59 @@ public:
         return where;
     }
 
+    // PICKING BY POSITION along an axis (np.take_along_axis / np.take): the consumer of what argmax, argsort and sort_with_index
+    // produce.  take_along_axis: `idx` is an SMArray<std::int64_t> of this array's rank whose other axes equal this array's
+    // or broadcast against them; result[..., j, ...] = (*this)[..., idx[..., j, ...], ...], of the broadcast shape with idx's
+    // extent on `axis`.  Without an axis both are flattened row-major.  take: `idx` is 1-D and the result has this array's
+    // shape with `axis` replaced by idx.size(); take_flat indexes the row-major flattening and gives shape {idx.size()}.
+    // `axis` counts from the end when negative; a bad axis, a rank mismatch or shapes that do not broadcast throw
+    // std::invalid_argument.  Both operands may be views or pending chains (evaluated first); the result is a dense array in
+    // HBM holding the operand's own bits, and feeds the next chain.  Each is ONE smhip_take_axis call (sm::fusion_stats().takes).
+    // index_mode::checked (the default) behaves like numpy: after the launch the one-word flag is downloaded -- a stream
+    // synchronisation -- and std::out_of_range is thrown if an index was outside [-R, R).  clip and wrap never wait; indices
+    // that came from argsort / argmax are valid by construction, so clip costs nothing there.
+    SMArray take_along_axis(const SMArray<std::int64_t> &idx, int axis, index_mode mode = index_mode::checked) const {
+        const std::size_t nd = _shape.size();
+        if (idx.shape().size() != nd)
+            throw std::invalid_argument("simpleMath/MI355X: take_along_axis: the index array has rank " + std::to_string(idx.shape().size()) +
+                                        ", the operand rank " + std::to_string(nd));
+        const int ax = take_axis_of(axis, nd);
+        hip::DeviceGuard on(device());
+        std::vector<std::int64_t> shape(nd), sa(nd), si(nd);
+        std::vector<std::size_t> result(nd);
+        for (std::size_t d = 0; d < nd; ++d) {
+            const std::size_t na = _shape[d], ni = idx.shape()[d];
+            if (static_cast<int>(d) == ax) {
+                result[d] = ni, sa[d] = static_cast<std::int64_t>(_strides[d]), si[d] = static_cast<std::int64_t>(idx.strides()[d]);
+            } else {
+                if (na != ni && na != 1 && ni != 1)
+                    throw std::invalid_argument("simpleMath/MI355X: take_along_axis: the shapes do not broadcast at axis " + std::to_string(d));
+                result[d] = na == 1 ? ni : na;
+                sa[d] = na == result[d] && na != 1 ? static_cast<std::int64_t>(_strides[d]) : 0;
+                si[d] = ni == result[d] && ni != 1 ? static_cast<std::int64_t>(idx.strides()[d]) : 0;
+            }
+            shape[d] = static_cast<std::int64_t>(result[d]);
+        }
+        return take_run(device_data(), idx.device_data(), shape, sa, si, ax, _shape[ax], mode, std::move(result));
+    }
+    SMArray take_along_axis(const SMArray<std::int64_t> &idx, index_mode mode = index_mode::checked) const {
+        return take_flat_of(idx, mode);
+    }
+    SMArray take(const SMArray<std::int64_t> &idx, int axis, index_mode mode = index_mode::checked) const {
+        if (idx.shape().size() != 1) throw std::invalid_argument("simpleMath/MI355X: take: the index array must be 1-D");
+        const std::size_t nd = _shape.size();
+        const int ax = take_axis_of(axis, nd);
+        hip::DeviceGuard on(device());
+        std::vector<std::int64_t> shape = hip::to_i64(_shape), sa = hip::to_i64(_strides), si(nd, 0);
+        std::vector<std::size_t> result(_shape);
+        result[ax] = idx.totalSize, shape[ax] = static_cast<std::int64_t>(idx.totalSize), si[ax] = static_cast<std::int64_t>(idx.strides()[0]);
+        return take_run(device_data(), idx.device_data(), shape, sa, si, ax, _shape[ax], mode, std::move(result));
+    }
+    SMArray take_flat(const SMArray<std::int64_t> &idx, index_mode mode = index_mode::checked) const {
+        if (idx.shape().size() != 1) throw std::invalid_argument("simpleMath/MI355X: take_flat: the index array must be 1-D");
+        return take_flat_of(idx, mode);
+    }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -1129,6 +1190,43 @@ private:
         hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, &n, &one, 1, 0,
                                    values ? values->device_data_mut() : nullptr, where ? where->device_data_mut() : nullptr));
         ++detail::tls_fusion_stats.sorts;
+    }
+
+    static int take_axis_of(int axis, std::size_t nd) {
+        const int n = static_cast<int>(nd), a = axis < 0 ? axis + n : axis;
+        if (a < 0 || a >= n) throw std::invalid_argument("simpleMath/MI355X: take: axis " + std::to_string(axis) + " out of range for rank " + std::to_string(n));
+        return a;
+    }
+    // Both operands in row-major order as one line each (views are made dense first), shape {idx.size()}.
+    SMArray take_flat_of(const SMArray<std::int64_t> &idx, index_mode mode) const {
+        hip::DeviceGuard on(device());
+        std::unique_ptr<SMArray> holder;
+        const T *in = dense_device(holder);
+        std::unique_ptr<SMArray<std::int64_t>> idx_holder;
+        if (!idx.is_dense()) idx_holder.reset(new SMArray<std::int64_t>(idx.contiguous()));
+        const std::int64_t *ix = idx_holder ? idx_holder->device_data() : idx.device_data();
+        const std::vector<std::int64_t> shape{static_cast<std::int64_t>(idx.totalSize)}, one{1};
+        return take_run(in, ix, shape, one, one, 0, totalSize, mode, std::vector<std::size_t>{idx.totalSize});
+    }
+    // `in` / `ix`: device pointers to the operands' first elements, pending chains already evaluated.
+    SMArray take_run(const T *in, const std::int64_t *ix, const std::vector<std::int64_t> &shape, const std::vector<std::int64_t> &sa,
+                     const std::vector<std::int64_t> &si, int axis, std::size_t extent, index_mode mode, std::vector<std::size_t> &&result) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "take / take_along_axis: f32, f64, i32 and i64");
+        hip::DeviceGuard on(device());
+        SMArray out = device_empty(std::move(result));
+        if (out.totalSize == 0) return out;
+        if (extent == 0) throw std::out_of_range("simpleMath/MI355X: take: cannot take from an axis of 0 elements");
+        hip::DeviceBuffer flag;  // one word from the pool, only when someone will read it
+        if (mode == index_mode::checked) flag = hip::DeviceBuffer(sizeof(std::int64_t));
+        hip::check(smhip_take_axis(static_cast<int>(mode), hip::dtype_of<T>::id, in, sa.data(), static_cast<std::int64_t>(extent), ix, si.data(), shape.data(),
+                                   static_cast<int>(shape.size()), axis, out.device_data_mut(), flag.template as<std::int64_t>()));
+        ++detail::tls_fusion_stats.takes;
+        if (mode == index_mode::checked) {
+            std::int64_t bad = 0;
+            hip::check(smhip_download(&bad, flag.get(), sizeof bad));  // waits for the stream
+            if (bad) throw std::out_of_range("simpleMath/MI355X: take: an index is out of bounds for an axis of " + std::to_string(extent) + " elements");
+        }
+        return out;
     }
 
     // Device pointer to a dense version of this array (itself when already dense).

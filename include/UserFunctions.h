@@ -278,6 +278,24 @@ SMArray<T> sort_flat(const SMArray<T> &arr, bool descending = false) { return ar
 template <typename T>
 SMArray<std::int64_t> argsort_flat(const SMArray<T> &arr, bool descending = false) { return arr.argsort_flat(descending); }
 
+// Picking by position along an axis (np.take_along_axis / np.take): result[..., j, ...] = arr[..., idx[..., j, ...], ...].
+// take_along_axis: `idx` has arr's rank, its other axes equal to arr's or broadcastable; without an axis both are flattened.
+// take: `idx` is 1-D, the result is arr's shape with `axis` replaced by idx.size(); take_flat indexes the row-major flattening.
+// `mode`: index_mode::checked (numpy's rule; throws std::out_of_range after a stream synchronisation), clip or wrap (asynchronous).
+// Semantics as SMArray::take_along_axis (SMArray.h) and smhip_take_axis (smhip.h).
+template <typename T>
+SMArray<T> take_along_axis(const SMArray<T> &arr, const SMArray<std::int64_t> &idx, int axis, index_mode mode = index_mode::checked) {
+    return arr.take_along_axis(idx, axis, mode);
+}
+template <typename T>
+SMArray<T> take_along_axis(const SMArray<T> &arr, const SMArray<std::int64_t> &idx, index_mode mode = index_mode::checked) {
+    return arr.take_along_axis(idx, mode);
+}
+template <typename T>
+SMArray<T> take(const SMArray<T> &arr, const SMArray<std::int64_t> &idx, int axis, index_mode mode = index_mode::checked) { return arr.take(idx, axis, mode); }
+template <typename T>
+SMArray<T> take_flat(const SMArray<T> &arr, const SMArray<std::int64_t> &idx, index_mode mode = index_mode::checked) { return arr.take_flat(idx, mode); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

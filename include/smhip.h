@@ -432,6 +432,49 @@ int smhip_sort_axis(int order, int dtype, const void *a, const int64_t *shape, c
 int smhip_sort_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
                     int *route, int *launches, int64_t *ori3, int64_t *chunk);
 
+/* ------------------------------------------------ take / take_along_axis */
+/* Picking by position along ONE axis, np.take_along_axis:  out[..., j, ...] = a[..., idx[..., j, ...], ...].  np.take(a, ids,
+ * axis) is the same call with the 1-D index array broadcast (stride 0) over every axis but `axis`.  The contract:
+ *   elements     f32, f64, i32 and i64.  The result holds the operand's own bits (which zero, which NaN payload): it is a copy,
+ *                never arithmetic, so it is unique, bit-exact and the same on every run and stream, whatever the route.
+ *   index modes  i = the int64 index read, R = a_extent:
+ *     CHECKED    if i < 0, i += R; then i is clamped to [0, R - 1].  If the clamp changed it (i < -R or i >= R originally) the
+ *                index was bad: the clamped element is still what is written, and with bad_out given any lane that meets a bad
+ *                index stores the constant 1 there (a plain store: every writer stores the same value).  The library sets
+ *                *bad_out to 0 in stream order before its launch, so after the call it reads 0 or 1.
+ *     CLIP       clamp(i, 0, R - 1): negatives go to 0, as np.take(mode="clip").
+ *     WRAP       i mod R with a non-negative result, as np.take(mode="wrap"); correct for INT64_MIN and INT64_MAX.
+ *   safety       in no mode does a kernel form an address outside `a`: the mode is applied to the 64-bit index before anything
+ *                is multiplied by a stride, and R >= 1 is checked here, so the position is always in [0, R - 1]. */
+typedef enum smhip_index_mode { SMHIP_INDEX_CHECKED = 0, SMHIP_INDEX_CLIP = 1, SMHIP_INDEX_WRAP = 2 } smhip_index_mode;
+/* `out_shape` (rank 1 .. SMHIP_MAX_NDIM) is the dense row-major result; out_shape[axis] = J, the number of indices per line.
+ * a_strides / idx_strides are in ELEMENTS, >= 0, against out_shape, and are 0 where that operand broadcasts (as smhip_broadcast
+ * returns them); a_strides[axis] is a's stride ALONG the gathered axis and a_extent = R its extent there.  idx is int64_t.
+ * bad_out_or_null: one int64_t in device memory.  Checked before any device is touched (SMHIP_ERR_INVALID): mode, dtype, ndim,
+ * axis outside [0, ndim) (not counted from the end), negative extents or strides, null out_shape / stride arrays, a_extent < 0,
+ * a_extent == 0 while the result is not empty (numpy raises), null a / idx / out, out overlapping a's span, idx's span or
+ * bad_out, bad_out overlapping idx's or a's span.  Any extent of 0 in out_shape is a no-op, whatever the pointers.
+ * Asynchronous, stream-ordered; recorded tiny operators are flushed first. */
+int smhip_take_axis(int mode, int dtype, const void *a, const int64_t *a_strides, int64_t a_extent,
+                    const int64_t *idx, const int64_t *idx_strides,
+                    const int64_t *out_shape, int ndim, int axis, void *out, int64_t *bad_out_or_null);
+/* Host only, no device touched: the route smhip_take_axis would take.  The axes of the result are ordered by a's stride and merged
+ * where a, idx and the result all run on; the walk is out[o, j, i] = a[o*sao + pick(idx[o*sio + j*sij + i*sii])*sar + i*sai] and
+ * oji3 = {O, J, I} its extents (the result's element count is O * J * I; O and I are the extents before and after the axis when
+ * the result is empty).  *route = a kernel id (SMHIP_TAKE_ROUTE_*) ORed with the flag below; *launches = the kernel launches of
+ * the call (the flag word is cleared by a memset, not a launch); *chunk = K, the longest line LINE stages in LDS, in elements
+ * (32 KiB: 8192 for 4-byte and 4096 for 8-byte elements).  Any output may be NULL.  The planner's test hook. */
+#define SMHIP_TAKE_ROUTE_NONE 0    /* an extent is 0: nothing to compute */
+#define SMHIP_TAKE_ROUTE_LINE 1    /* I = 1, a's line contiguous, R <= K and J >= R / c: the line is staged in LDS and picked from there */
+#define SMHIP_TAKE_ROUTE_ROWS 2    /* a's and the result's rows of I >= one 16-byte vector are contiguous and the index does not vary along
+                                      them: whole rows are copied, the index read once per row */
+#define SMHIP_TAKE_ROUTE_DIRECT 3  /* everything else: one element per lane along the result's unit stride; the read of a is uncoalesced */
+#define SMHIP_TAKE_COPY 0x100      /* a and / or idx do not merge to the three-axis walk and are copied dense first (one launch each); a
+                                      transposed or a broadcast operand never needs it */
+int smhip_take_plan(int mode, int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides,
+                    const int64_t *out_shape, int ndim, int axis,
+                    int *route, int *launches, int64_t *oji3, int64_t *chunk);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

@@ -52,6 +52,11 @@ SORT_ASCENDING, SORT_DESCENDING = range(2)  # smhip_sort_order
 # smhip_sort_plan's route word: a kernel id in the low byte, flags above it
 SORT_ROUTE_NONE, SORT_ROUTE_COPYONLY, SORT_ROUTE_ROW = range(3)
 SORT_MERGE, SORT_COPY = 0x100, 0x200
+INDEX_CHECKED, INDEX_CLIP, INDEX_WRAP = range(3)  # smhip_index_mode
+INDEX_MODES = {"checked": INDEX_CHECKED, "raise": INDEX_CHECKED, "clip": INDEX_CLIP, "wrap": INDEX_WRAP}
+# smhip_take_plan's route word: a kernel id in the low byte, the flag above it
+TAKE_ROUTE_NONE, TAKE_ROUTE_LINE, TAKE_ROUTE_ROWS, TAKE_ROUTE_DIRECT = range(4)
+TAKE_COPY = 0x100
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -728,6 +733,102 @@ class Smhip:
         self._ck(self.c.smhip_sort_plan(C.c_int(SORT_DESCENDING if descending else SORT_ASCENDING), C.c_int(dtype), _i64(shape), _i64(strides),
                                         C.c_int(len(shape)), C.c_int(int(axis)), C.byref(route), C.byref(launches), ori, C.byref(chunk)))
         return route.value, launches.value, tuple(int(x) for x in ori), chunk.value
+
+    def take_along_axis(self, a: DeviceArray, idx: DeviceArray, axis, mode="checked", out: DeviceArray | None = None):
+        """np.take_along_axis(a, idx, axis): out[..., j, ...] = a[..., idx[..., j, ...], ...] -> a new dense DeviceArray (or into
+        `out`, a dense array of a's dtype and the result's element count, never an operand).  `idx` is an int64 DeviceArray of
+        a's rank whose other axes equal a's or broadcast against them; both may be views.  axis=None flattens both row-major.
+        mode: "checked" (numpy's rule: negatives count from the end, anything else out of range raises IndexError -- after
+        reading the one-word flag, which waits for the stream), "clip" or "wrap" (np.take's, fully asynchronous)."""
+        self._take_dtypes(a, idx)
+        if axis is None:
+            a, idx = self._flat(a), self._flat(idx)
+            axis = 0
+        if a.ndim != idx.ndim:
+            raise ValueError(f"take_along_axis: a has rank {a.ndim}, idx rank {idx.ndim}")
+        (axis,) = self._axes(a.ndim, int(axis))
+        shape, sa, si = [], [], []
+        for d in range(a.ndim):
+            na, ni = a.shape[d], idx.shape[d]
+            if d == axis:
+                shape.append(ni), sa.append(a.strides[d]), si.append(idx.strides[d])
+                continue
+            if na != ni and na != 1 and ni != 1:
+                raise ValueError(f"take_along_axis: shapes {a.shape} and {idx.shape} do not broadcast at axis {d}")
+            n = ni if na == 1 else na
+            shape.append(n), sa.append(a.strides[d] if na == n and n != 1 else 0), si.append(idx.strides[d] if ni == n and n != 1 else 0)
+        return self._take(a, idx, sa, a.shape[axis], si, shape, axis, mode, out, tuple(shape), "take_along_axis")
+
+    def take(self, a: DeviceArray, idx: DeviceArray, axis=None, mode="checked", out: DeviceArray | None = None):
+        """np.take(a, idx, axis): a's shape with `axis` replaced by idx's shape (idx is an int64 DeviceArray, 1-D in the C ABI's
+        terms; an N-D one is flattened and the result reshaped, as numpy does).  axis=None indexes a's row-major flattening.
+        mode and out as in take_along_axis()."""
+        self._take_dtypes(a, idx)
+        if axis is None:
+            a, axis = self._flat(a), 0
+        (axis,) = self._axes(a.ndim, int(axis))
+        if out is idx:
+            raise ValueError("take: out must not be an operand")
+        flat = idx if idx.ndim == 1 else self._flat(idx)
+        shape = list(a.shape)
+        shape[axis] = flat.size
+        si = [0] * a.ndim
+        si[axis] = flat.strides[0]
+        result_shape = a.shape[:axis] + idx.shape + a.shape[axis + 1:]
+        return self._take(a, flat, list(a.strides), a.shape[axis], si, shape, axis, mode, out, result_shape, "take")
+
+    def _take_dtypes(self, a, idx):
+        if a.dtype not in DTYPES:
+            raise ValueError(f"take: dtype {a.dtype} (f32, f64, i32 and i64 only)")
+        if idx.dtype != np.dtype(np.int64):
+            raise ValueError(f"take: the index array must be int64, got {idx.dtype}")
+
+    def _flat(self, a):
+        """`a` in row-major order as a 1-D array: a view is copied dense first."""
+        if not a.is_dense():
+            dense = self.empty(a.shape, a.dtype)
+            self.assign(dense, a)
+            a = dense
+        return DeviceArray(self, a.base_ptr, a.dtype, (a.size,), (1,), a.offset, a._owner)
+
+    def _take(self, a, idx, sa, extent, si, shape, axis, mode, out, result_shape, who):
+        if mode not in INDEX_MODES:
+            raise ValueError(f"{who}: mode {mode!r} (one of 'checked', 'clip', 'wrap')")
+        n = int(np.prod(shape, dtype=np.int64))
+        if out is None:
+            out = self.empty(result_shape, a.dtype)
+        elif out is a or out is idx:
+            raise ValueError(f"{who}: out must not be an operand")
+        elif out.dtype != a.dtype or out.size != n or not out.is_dense():
+            raise ValueError(f"{who}: out must be a dense {a.dtype} array of {n} elements (shape {tuple(result_shape)}); "
+                             f"got {out.dtype} {out.shape} dense={out.is_dense()}")
+        if n and extent == 0:
+            raise IndexError(f"{who}: cannot take from an axis of 0 elements")
+        checked = INDEX_MODES[mode] == INDEX_CHECKED and n > 0
+        flag = self.empty((1,), np.int64) if checked else None
+        self._ck(self.c.smhip_take_axis(C.c_int(INDEX_MODES[mode]), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(sa), C.c_int64(extent),
+                                        C.c_void_p(idx.ptr), _i64(si), _i64(shape), C.c_int(len(shape)), C.c_int(axis), C.c_void_p(out.ptr),
+                                        C.c_void_p(flag.ptr if checked else 0)))
+        if checked and int(flag.numpy()[0]):
+            raise IndexError(f"{who}: an index is out of bounds for axis {axis} with size {extent}")
+        return out
+
+    def take_raw(self, mode, dtype, a_ptr, a_strides, a_extent, idx_ptr, idx_strides, out_shape, axis, out_ptr, bad_ptr=0, ndim=None):
+        """smhip_take_axis with every argument as given (argument-validation tests); ndim defaults to len(out_shape)."""
+        if ndim is None:
+            ndim = len(out_shape) if out_shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        return self.c.smhip_take_axis(C.c_int(mode), C.c_int(dtype), C.c_void_p(a_ptr), arr(a_strides), C.c_int64(a_extent), C.c_void_p(idx_ptr),
+                                      arr(idx_strides), arr(out_shape), C.c_int(ndim), C.c_int(axis), C.c_void_p(out_ptr), C.c_void_p(bad_ptr))
+
+    def take_plan(self, dtype, a_strides, a_extent, idx_strides, out_shape, axis, mode="clip"):
+        """smhip_take_plan (host only): (route word, launches, (O, J, I), K) for a call with these strides (elements) over out_shape."""
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        mode = INDEX_MODES[mode] if not isinstance(mode, int) else mode
+        route, launches, oji, chunk = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), C.c_int64(0)
+        self._ck(self.c.smhip_take_plan(C.c_int(mode), C.c_int(dtype), _i64(a_strides), C.c_int64(int(a_extent)), _i64(idx_strides), _i64(out_shape),
+                                        C.c_int(len(out_shape)), C.c_int(int(axis)), C.byref(route), C.byref(launches), oji, C.byref(chunk)))
+        return route.value, launches.value, tuple(int(x) for x in oji), chunk.value
 
     def sum(self, a: DeviceArray):
         out = C.c_double(0)

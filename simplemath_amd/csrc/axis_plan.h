@@ -1,5 +1,5 @@
-// axis_plan.h -- the host-side planner toolbox of the three axis families: reduce_axis.hip (sum, mean, max, min), scan_axis.hip
-// (cumulative scans) and argreduce_axis.hip (argmax / argmin).  Each rule they share is written here once:
+// axis_plan.h -- the host-side planner toolbox of the axis families: reduce_axis.hip (sum, mean, max, min), scan_axis.hip
+// (cumulative scans), argreduce_axis.hip (argmax / argmin), sort_axis.hip and take_axis.hip.  Each rule they share is written here once:
 //   * the merging of a view's axes and the canonical walk out[o, i] = f_r a[o*so + r*sr + i*si] it may come to (Canon, ROW / COLUMN);
 //   * lanes per short row (segment_lanes) and the cutting of R into chunks when a launch would have too few lanes (split_row,
 //     split_column);
@@ -48,23 +48,27 @@ inline bool row_major(const int64_t *shape, const int64_t *strides, int ndim) {
     return true;
 }
 
-struct Ax { int64_t n, st, ost; bool red; };
+struct Ax { int64_t n, st, ost; bool red; int64_t st2 = 0; };
 
 // Axes of extent > 1, ordered by stride (largest first, ties in index order), neighbours merged where memory -- and for kept
 // axes the dense result -- runs on without a gap.  Returns the count.
-inline int merge_axes(const int64_t *shape, const int64_t *strides, int ndim, uint32_t mask, bool by_index, Ax *ax) {
+// The gather (take_axis.hip) walks a result that keeps the named axis and reads a second operand: `result_strides` stands in
+// for the dense strides over the kept axes, and `second` is that operand's strides, which must run on as well (Ax::st2).
+inline int merge_axes(const int64_t *shape, const int64_t *strides, int ndim, uint32_t mask, bool by_index, Ax *ax,
+                      const int64_t *result_strides = nullptr, const int64_t *second = nullptr) {
     int64_t ost[SMHIP_MAX_NDIM];
     dense_strides(shape, ndim, ost, ~mask);
     int n = 0;
     for (int d = 0; d < ndim; ++d)
-        if (shape[d] > 1) ax[n++] = Ax{shape[d], strides[d], ost[d], (mask >> d & 1) != 0};
+        if (shape[d] > 1) ax[n++] = Ax{shape[d], strides[d], result_strides ? result_strides[d] : ost[d], (mask >> d & 1) != 0, second ? second[d] : 0};
     if (!by_index) std::stable_sort(ax, ax + n, [](const Ax &x, const Ax &y) { return x.st > y.st; });
     int m = 0;
     for (int k = 0; k < n; ++k) {
         if (m > 0) {
             Ax &prev = ax[m - 1];
-            if (prev.red == ax[k].red && prev.st == ax[k].st * ax[k].n && (prev.red || prev.ost == ax[k].ost * ax[k].n)) {
-                prev.n *= ax[k].n, prev.st = ax[k].st, prev.ost = ax[k].ost;
+            if (prev.red == ax[k].red && prev.st == ax[k].st * ax[k].n && (prev.red || prev.ost == ax[k].ost * ax[k].n) &&
+                prev.st2 == ax[k].st2 * ax[k].n) {
+                prev.n *= ax[k].n, prev.st = ax[k].st, prev.ost = ax[k].ost, prev.st2 = ax[k].st2;
                 continue;
             }
         }

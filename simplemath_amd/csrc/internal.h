@@ -243,4 +243,12 @@ void sort_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int
 int launch_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *values_out,
                      int64_t *index_out, hipStream_t s);
 
+// take_axis.hip: take / take_along_axis, the gather along an axis by int64 positions (smhip_take_axis); the checks and the planner are host-only
+int take_axis_check(const char *who, int mode, int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape,
+                    int ndim, int axis);
+void take_axis_plan(int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape, int ndim, int axis,
+                    int *route, int *launches, int64_t *oji3, int64_t *chunk);
+int launch_take_axis(int mode, int dtype, const void *a, const int64_t *a_strides, int64_t a_extent, const int64_t *idx, const int64_t *idx_strides,
+                     const int64_t *out_shape, int ndim, int axis, void *out, int64_t *bad_out, hipStream_t s);
+
 }  // namespace smhip
