@@ -101,6 +101,7 @@ struct FusionStats {
     unsigned long long arg_reductions = 0;      // smhip_argreduce_axis calls: argmax / argmin / max_with_index / min_with_index
     unsigned long long sorts = 0;               // smhip_sort_axis calls: sort / argsort / sort_with_index and their _flat forms
     unsigned long long takes = 0;               // smhip_take_axis calls: take / take_along_axis / take_flat
+    unsigned long long scatters = 0;            // smhip_scatter_axis calls: put_along_axis / put / put_flat / scatter_add / index_add
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -856,6 +857,62 @@ public:
         return take_flat_of(idx, mode);
     }
 
+    // WRITING BY POSITION along an axis, IN PLACE on this array (np.put_along_axis / np.put, np.add.at; torch's scatter_add_ /
+    // index_add_): the transpose of take.  put_along_axis / scatter_add: `idx` is an SMArray<std::int64_t> of this array's rank
+    // whose other axes equal this array's or are 1; (*this)[..., pick(idx[..., j, ...]), ...] = (or +=) values[..., j, ...];
+    // `values` broadcasts against the walk shape (this array's shape with idx's extent on `axis`) or is a scalar T.  Without an
+    // axis the array and idx are flattened row-major, and so are the values: in the flat forms (this one and put_flat) they have
+    // idx's element count, or one element, or are a scalar -- nothing else broadcasts against a line.  put / index_add: `ids` is 1-D, `values` has this array's shape with `axis`
+    // replaced by ids.size(), or broadcasts to it, or is a scalar; put_flat indexes the row-major flattening.
+    // The rule for duplicates is fixed by the data, so the result is the same bits on every run: PUT -- among the entries of a
+    // line that name the same position the one with the largest j wins (numpy's sequential assignment); ADD -- a destination's
+    // contributions are added one by one in ascending j, f32 in fp64 rounded once.  unique = true is the caller's promise that
+    // no two entries of a line name the same position (a permutation from argsort, an argmax with keepdims): one launch, no sort.
+    // `axis` counts from the end when negative; a bad axis, a rank mismatch or shapes that do not broadcast throw
+    // std::invalid_argument.  Operands may be views or pending chains (evaluated first).  A target that is not dense row-major
+    // (a strided slice, a transpose) is staged: dense copy, scatter, strided assignment back.  Each is ONE smhip_scatter_axis call
+    // (sm::fusion_stats().scatters).  index_mode::checked (the default): negatives count from the end, an entry outside [-R, R) is
+    // DROPPED, and after the launches the one-word flag is downloaded -- a stream synchronisation -- and std::out_of_range thrown;
+    // THE VALID ENTRIES HAVE BEEN APPLIED BY THEN.  clip and wrap never wait.  All forms return *this.
+    SMArray &put_along_axis(const SMArray<std::int64_t> &idx, const SMArray &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_along(SMHIP_SCATTER_PUT, idx, &values, T{}, axis, mode, unique);
+    }
+    SMArray &put_along_axis(const SMArray<std::int64_t> &idx, T value, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_along(SMHIP_SCATTER_PUT, idx, nullptr, value, axis, mode, unique);
+    }
+    SMArray &put_along_axis(const SMArray<std::int64_t> &idx, const SMArray &values, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_flat(SMHIP_SCATTER_PUT, idx, &values, T{}, mode, unique);
+    }
+    SMArray &put_along_axis(const SMArray<std::int64_t> &idx, T value, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_flat(SMHIP_SCATTER_PUT, idx, nullptr, value, mode, unique);
+    }
+    SMArray &scatter_add(const SMArray<std::int64_t> &idx, const SMArray &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_along(SMHIP_SCATTER_ADD, idx, &values, T{}, axis, mode, unique);
+    }
+    SMArray &scatter_add(const SMArray<std::int64_t> &idx, T value, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_along(SMHIP_SCATTER_ADD, idx, nullptr, value, axis, mode, unique);
+    }
+    SMArray &put(const SMArray<std::int64_t> &ids, const SMArray &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_ids(SMHIP_SCATTER_PUT, ids, &values, T{}, axis, mode, unique);
+    }
+    SMArray &put(const SMArray<std::int64_t> &ids, T value, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_ids(SMHIP_SCATTER_PUT, ids, nullptr, value, axis, mode, unique);
+    }
+    SMArray &put_flat(const SMArray<std::int64_t> &ids, const SMArray &values, index_mode mode = index_mode::checked, bool unique = false) {
+        if (ids.shape().size() != 1) throw std::invalid_argument("simpleMath/MI355X: put_flat: the index array must be 1-D");
+        return scatter_flat(SMHIP_SCATTER_PUT, ids, &values, T{}, mode, unique);
+    }
+    SMArray &put_flat(const SMArray<std::int64_t> &ids, T value, index_mode mode = index_mode::checked, bool unique = false) {
+        if (ids.shape().size() != 1) throw std::invalid_argument("simpleMath/MI355X: put_flat: the index array must be 1-D");
+        return scatter_flat(SMHIP_SCATTER_PUT, ids, nullptr, value, mode, unique);
+    }
+    SMArray &index_add(const SMArray<std::int64_t> &ids, const SMArray &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_ids(SMHIP_SCATTER_ADD, ids, &values, T{}, axis, mode, unique);
+    }
+    SMArray &index_add(const SMArray<std::int64_t> &ids, T value, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+        return scatter_ids(SMHIP_SCATTER_ADD, ids, nullptr, value, axis, mode, unique);
+    }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -1227,6 +1284,123 @@ private:
             if (bad) throw std::out_of_range("simpleMath/MI355X: take: an index is out of bounds for an axis of " + std::to_string(extent) + " elements");
         }
         return out;
+    }
+
+    // ---- scatter: the walk shape is this array's shape with `axis` replaced by the entries per line
+    SMArray &scatter_along(int kind, const SMArray<std::int64_t> &idx, const SMArray *values, T scalar, int axis, index_mode mode, bool unique) {
+        const std::size_t nd = _shape.size();
+        if (idx.shape().size() != nd)
+            throw std::invalid_argument("simpleMath/MI355X: put_along_axis / scatter_add: the index array has rank " + std::to_string(idx.shape().size()) +
+                                        ", the target rank " + std::to_string(nd));
+        const int ax = take_axis_of(axis, nd);
+        std::vector<std::int64_t> walk(nd), si(nd);
+        for (std::size_t d = 0; d < nd; ++d) {
+            const std::size_t na = _shape[d], ni = idx.shape()[d];
+            const bool along = static_cast<int>(d) == ax;
+            if (!along && ni != na && ni != 1)
+                throw std::invalid_argument("simpleMath/MI355X: put_along_axis / scatter_add: the index array does not match the target at axis " + std::to_string(d));
+            walk[d] = static_cast<std::int64_t>(along ? ni : na);
+            si[d] = along || (ni == na && na != 1) ? static_cast<std::int64_t>(idx.strides()[d]) : 0;
+        }
+        return scatter_run(kind, walk, ax, idx, si, values, scalar, mode, unique);
+    }
+    SMArray &scatter_ids(int kind, const SMArray<std::int64_t> &ids, const SMArray *values, T scalar, int axis, index_mode mode, bool unique) {
+        if (ids.shape().size() != 1) throw std::invalid_argument("simpleMath/MI355X: put / index_add: the index array must be 1-D");
+        const std::size_t nd = _shape.size();
+        const int ax = take_axis_of(axis, nd);
+        std::vector<std::int64_t> walk = hip::to_i64(_shape), si(nd, 0);
+        walk[ax] = static_cast<std::int64_t>(ids.totalSize), si[ax] = static_cast<std::int64_t>(ids.strides()[0]);
+        return scatter_run(kind, walk, ax, ids, si, values, scalar, mode, unique);
+    }
+    // This array and idx in row-major order as one line each.
+    SMArray &scatter_flat(int kind, const SMArray<std::int64_t> &idx, const SMArray *values, T scalar, index_mode mode, bool unique) {
+        if (!is_dense()) return staged([&](SMArray &dense) { dense.scatter_flat(kind, idx, values, scalar, mode, unique); });
+        std::unique_ptr<SMArray<std::int64_t>> idx_holder;
+        if (!idx.is_dense()) idx_holder.reset(new SMArray<std::int64_t>(idx.contiguous()));
+        std::unique_ptr<SMArray> val_line;
+        if (values) {
+            val_line.reset(new SMArray(values->is_dense() ? values->alias() : values->contiguous()));
+            val_line->as_line();
+        }
+        SMArray line = alias();
+        line.as_line();
+        line.scatter_run(kind, {static_cast<std::int64_t>(idx.totalSize)}, 0, idx_holder ? *idx_holder : idx, {1}, val_line.get(), scalar, mode, unique);
+        return *this;
+    }
+    // A dense array seen as one line of totalSize elements.
+    void as_line() { _shape = {totalSize}, _strides = {1}, ndim = 1; }
+    // fn on a dense copy of this array, assigned back element by element -- also when fn throws for a bad index under
+    // index_mode::checked: the valid entries have been applied.
+    template <typename Fn> SMArray &staged(Fn &&fn) {
+        SMArray dense = contiguous();
+        try {
+            fn(dense);
+        } catch (const std::out_of_range &) {
+            *this = std::move(dense);
+            throw;
+        }
+        *this = std::move(dense);
+        return *this;
+    }
+    SMArray &scatter_run(int kind, const std::vector<std::int64_t> &walk, int axis, const SMArray<std::int64_t> &idx, const std::vector<std::int64_t> &si,
+                         const SMArray *values, T scalar, index_mode mode, bool unique) {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "put / put_along_axis / scatter_add / index_add: f32, f64, i32 and i64");
+        const std::size_t nd = walk.size();
+        // values against the walk shape, aligned at the last axis
+        std::vector<std::int64_t> sv(nd, 0);
+        if (values) {
+            const std::size_t nv = values->_shape.size();
+            if (nv > nd) throw std::invalid_argument("simpleMath/MI355X: scatter: the values have a higher rank than the target");
+            for (std::size_t d = 0; d < nv; ++d) {
+                const std::size_t w = static_cast<std::size_t>(walk[nd - nv + d]), n = values->_shape[d];
+                if (n != w && n != 1) throw std::invalid_argument("simpleMath/MI355X: scatter: the values do not broadcast at axis " + std::to_string(nd - nv + d));
+                sv[nd - nv + d] = n == w && w != 1 ? static_cast<std::int64_t>(values->_strides[d]) : 0;
+            }
+        }
+        std::int64_t entries = 1;
+        for (std::int64_t w : walk) entries *= w;
+        if (entries == 0) return *this;
+        if (_shape[axis] == 0) throw std::out_of_range("simpleMath/MI355X: scatter: cannot place entries on an axis of 0 elements");
+        if (!is_dense())
+            return staged([&](SMArray &dense) { dense.scatter_run(kind, walk, axis, idx, si, values, scalar, mode, unique); });
+        hip::DeviceGuard on(device());
+        // an operand that shares the target's storage is copied first: the C ABI refuses the overlap
+        std::unique_ptr<SMArray> val_holder;
+        std::unique_ptr<SMArray<std::int64_t>> idx_holder;
+        std::vector<std::int64_t> si_used(si);
+        if (values && values->data.storage() == data.storage()) {
+            val_holder.reset(new SMArray(values->contiguous()));
+            for (std::size_t d = 0, nv = values->_shape.size(); d < nv; ++d)
+                if (sv[nd - nv + d]) sv[nd - nv + d] = static_cast<std::int64_t>(val_holder->_strides[d]);
+            values = val_holder.get();
+        } else if (!values) {
+            val_holder.reset(new SMArray(device_full(std::vector<std::size_t>{1}, scalar)));
+            values = val_holder.get();
+        }
+        if constexpr (std::is_same_v<T, std::int64_t>) {
+            if (idx.data.storage() == data.storage()) {
+                idx_holder.reset(new SMArray<std::int64_t>(idx.contiguous()));
+                for (std::size_t d = 0; d < nd; ++d)  // the copy is dense: a line (1-D ids, a flattened idx) has stride 1
+                    if (si_used[d]) si_used[d] = idx.shape().size() == nd ? static_cast<std::int64_t>(idx_holder->strides()[d]) : 1;
+            }
+        }
+        const T *vp = values->device_data();  // pending chains that produce the operands run here
+        const std::int64_t *ip = idx_holder ? idx_holder->device_data() : idx.device_data();
+        const auto out_shape = hip::to_i64(_shape);
+        hip::DeviceBuffer flag;  // one word from the pool, only when someone will read it
+        if (mode == index_mode::checked) flag = hip::DeviceBuffer(sizeof(std::int64_t));
+        hip::check(smhip_scatter_axis(kind, static_cast<int>(mode), unique ? SMHIP_SCATTER_UNIQUE : 0, hip::dtype_of<T>::id,
+                                      data.storage()->dev_rw() + data.offset(), out_shape.data(), static_cast<int>(nd), axis, ip, si_used.data(), vp, sv.data(),
+                                      walk[axis], flag.template as<std::int64_t>()));
+        ++detail::tls_fusion_stats.scatters;
+        if (mode == index_mode::checked) {
+            std::int64_t bad = 0;
+            hip::check(smhip_download(&bad, flag.get(), sizeof bad));  // waits for the stream
+            if (bad)
+                throw std::out_of_range("simpleMath/MI355X: scatter: an index is out of bounds for an axis of " + std::to_string(_shape[axis]) +
+                                        " elements (the valid entries have been applied)");
+        }
+        return *this;
     }
 
     // Device pointer to a dense version of this array (itself when already dense).

@@ -296,6 +296,38 @@ SMArray<T> take(const SMArray<T> &arr, const SMArray<std::int64_t> &idx, int axi
 template <typename T>
 SMArray<T> take_flat(const SMArray<T> &arr, const SMArray<std::int64_t> &idx, index_mode mode = index_mode::checked) { return arr.take_flat(idx, mode); }
 
+// Writing by position along an axis, in place on `arr` (np.put_along_axis / np.put, np.add.at): the transpose of take.  `values` is
+// an SMArray<T> that broadcasts against the walk shape, or a scalar.  put_along_axis / scatter_add: `idx` has arr's rank, its other
+// axes equal to arr's or 1; without an axis arr, idx and the values are flattened (values of idx's size, one element or a scalar).  put / index_add: `ids` is 1-D; put_flat indexes the
+// row-major flattening.  Duplicates: PUT -- the entry with the largest position along idx wins; ADD -- contributions are added
+// one by one in that order (f32 in fp64), so every run gives the same bits.  `unique` promises that no two entries of a line name
+// the same position (one launch, no sort).  `mode` as for take; under checked a bad entry is dropped and std::out_of_range thrown
+// after the valid ones have been applied.  All return arr.  Semantics as SMArray::put_along_axis (SMArray.h) and smhip_scatter_axis.
+template <typename T, typename V>
+SMArray<T> &put_along_axis(SMArray<T> &arr, const SMArray<std::int64_t> &idx, const V &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+    return arr.put_along_axis(idx, values, axis, mode, unique);
+}
+template <typename T, typename V>
+SMArray<T> &put_along_axis(SMArray<T> &arr, const SMArray<std::int64_t> &idx, const V &values, index_mode mode = index_mode::checked, bool unique = false) {
+    return arr.put_along_axis(idx, values, mode, unique);
+}
+template <typename T, typename V>
+SMArray<T> &scatter_add(SMArray<T> &arr, const SMArray<std::int64_t> &idx, const V &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+    return arr.scatter_add(idx, values, axis, mode, unique);
+}
+template <typename T, typename V>
+SMArray<T> &put(SMArray<T> &arr, const SMArray<std::int64_t> &ids, const V &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+    return arr.put(ids, values, axis, mode, unique);
+}
+template <typename T, typename V>
+SMArray<T> &put_flat(SMArray<T> &arr, const SMArray<std::int64_t> &ids, const V &values, index_mode mode = index_mode::checked, bool unique = false) {
+    return arr.put_flat(ids, values, mode, unique);
+}
+template <typename T, typename V>
+SMArray<T> &index_add(SMArray<T> &arr, const SMArray<std::int64_t> &ids, const V &values, int axis, index_mode mode = index_mode::checked, bool unique = false) {
+    return arr.index_add(ids, values, axis, mode, unique);
+}
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

@@ -475,6 +475,63 @@ int smhip_take_plan(int mode, int dtype, const int64_t *a_strides, int64_t a_ext
                     const int64_t *out_shape, int ndim, int axis,
                     int *route, int *launches, int64_t *oji3, int64_t *chunk);
 
+/* ------------------------- put_along_axis / put / scatter_add / index_add */
+/* Writing by position along ONE axis, in place.  For an axis of R elements, idx is int64_t and holds J entries per line, walked in
+ * ascending position j; every other axis broadcasts as in smhip_take_axis.  The contract:
+ *   index modes  smhip_index_mode.  CLIP and WRAP exactly as in smhip_take_axis.  CHECKED: a negative index counts from the end; an
+ *                index outside [-R, R) is bad and its entry is DROPPED: it writes and adds nothing.  With bad_out given, any lane
+ *                that meets a bad index stores the constant 1 there (a plain store of one value); the library sets *bad_out to 0
+ *                in stream order before its launches, so after the call it reads 0 or 1.
+ *   safety       in no mode is an address outside `out` formed: the mode is applied to the 64-bit index before anything is
+ *                multiplied by a stride.
+ *   PUT          np.put_along_axis: out[..., p, ...] = values[..., j, ...] with p = pick(idx[..., j, ...]).  Among the entries of
+ *                one line that name the same position THE ONE WITH THE LARGEST j WINS (numpy's sequential assignment).  The
+ *                result holds the winning value's own bits (which zero, which NaN payload).  Destinations that no entry names
+ *                are not written.
+ *   ADD          np.add.at along an axis (torch's scatter_add_ / index_add_): for every destination named by at least one entry,
+ *                acc = out[p]; its contributions are added ONE BY ONE IN ASCENDING j; one store.  f32 accumulates in fp64 and is
+ *                rounded to f32 once (the family rule of smhip_reduce_axes); f64 in fp64; i32 / i64 wrap in the type's width.
+ *                The order is fixed by the data, so the result is unique: the same bits on every run, stream and grid (a NaN
+ *                result's payload apart).  Destinations no entry names keep their bits.  There are no atomics.
+ *   UNIQUE       SMHIP_SCATTER_UNIQUE in `flags` is the caller's promise that no two entries of a line name the same position
+ *                after the mode is applied (a permutation from argsort, an argmax with keepdims).  The call then needs no sort and
+ *                is one launch.  If the promise is broken, PUT leaves one of the candidates and ADD may lose contributions, both
+ *                depending on the run; still no address outside `out` is formed and bad_out works.  A line of J <= 1 entries is
+ *                unique by construction and takes the unique routes without the flag.
+ *   types        f32, f64, i32 and i64. */
+typedef enum smhip_scatter_kind { SMHIP_SCATTER_PUT = 0, SMHIP_SCATTER_ADD = 1 } smhip_scatter_kind;
+#define SMHIP_SCATTER_UNIQUE 1
+/* `out` is dense row-major over out_shape (rank 1 .. SMHIP_MAX_NDIM) and is updated in place; out_shape[axis] = R.  The WALK SHAPE is
+ * out_shape with `axis` replaced by n_entries = J.  idx_strides / val_strides are in ELEMENTS, >= 0, against the walk shape, 0 where
+ * the operand broadcasts: a 1-D `ids` (the inverse of np.take) is stride 0 on every axis but `axis`, a scalar value all zeros.
+ * bad_out_or_null: one int64_t in device memory.  Checked before any device is touched (SMHIP_ERR_INVALID): kind, mode, unknown
+ * flag bits, dtype, ndim, axis outside [0, ndim) (not counted from the end), negative extents or strides, J < 0, null arrays or
+ * pointers, R == 0 with entries to place, spans past 2^59 elements, out overlapping idx's span, values' span or bad_out, bad_out
+ * overlapping idx or values.  J >= 2^31 without the unique routes is SMHIP_ERR_UNSUPPORTED (the sort's limit).  Any extent of 0 in
+ * the walk shape (J = 0 included) is a no-op, whatever the pointers.  Asynchronous, stream-ordered; recorded tiny operators are
+ * flushed first. */
+int smhip_scatter_axis(int kind, int mode, int flags, int dtype,
+                       void *out, const int64_t *out_shape, int ndim, int axis,
+                       const int64_t *idx, const int64_t *idx_strides,
+                       const void *values, const int64_t *val_strides, int64_t n_entries,
+                       int64_t *bad_out_or_null);
+/* Host only, no device touched: the route smhip_scatter_axis would take.  The walk is [O] J [I] over the dense target:
+ * out[o, pick(idx[o*sio + j*sij + i*sii]), i] <- values[o*svo + j*svj + i*svi]; orji4 = {O, R, J, I}.  *route = a kernel id
+ * (SMHIP_SCATTER_ROUTE_*) ORed with the flag below; *launches = every kernel launch of the call, the sort's included (the flag word
+ * is cleared by a memset, not a launch); *sorted_entries = the index entries actually sorted -- J for a 1-D ids, not O * J * I --
+ * and 0 on the unique routes.  The mode does not enter the plan.  Any output may be NULL.  The planner's test hook. */
+#define SMHIP_SCATTER_ROUTE_NONE 0         /* an extent is 0: nothing to do */
+#define SMHIP_SCATTER_ROUTE_DIRECT 1       /* unique: one entry per lane along the unit stride of the walk, one launch */
+#define SMHIP_SCATTER_ROUTE_ROWS 2         /* unique; idx constant along contiguous rows of I >= one 16-byte vector in values and out:
+                                              whole rows move, the index read once per row */
+#define SMHIP_SCATTER_ROUTE_SORTED 3       /* no promise: normalise, stable sort of (position, j), then a lane per sorted entry */
+#define SMHIP_SCATTER_ROUTE_SORTED_ROWS 4  /* no promise; the same row condition as ROWS: a lane segment per sorted entry and its row */
+#define SMHIP_SCATTER_COPY 0x100           /* idx and / or values do not merge to the [O] J [I] walk and are copied dense first (one
+                                              launch each) */
+int smhip_scatter_plan(int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis,
+                       const int64_t *idx_strides, const int64_t *val_strides, int64_t n_entries,
+                       int *route, int *launches, int64_t *orji4, int64_t *sorted_entries);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

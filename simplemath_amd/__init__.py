@@ -57,6 +57,11 @@ INDEX_MODES = {"checked": INDEX_CHECKED, "raise": INDEX_CHECKED, "clip": INDEX_C
 # smhip_take_plan's route word: a kernel id in the low byte, the flag above it
 TAKE_ROUTE_NONE, TAKE_ROUTE_LINE, TAKE_ROUTE_ROWS, TAKE_ROUTE_DIRECT = range(4)
 TAKE_COPY = 0x100
+SCATTER_PUT, SCATTER_ADD = range(2)  # smhip_scatter_kind
+SCATTER_UNIQUE = 1                   # smhip_scatter_axis's flag: no two entries of a line name the same position
+# smhip_scatter_plan's route word: a kernel id in the low byte, the flag above it
+SCATTER_ROUTE_NONE, SCATTER_ROUTE_DIRECT, SCATTER_ROUTE_ROWS, SCATTER_ROUTE_SORTED, SCATTER_ROUTE_SORTED_ROWS = range(5)
+SCATTER_COPY = 0x100
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -829,6 +834,122 @@ class Smhip:
         self._ck(self.c.smhip_take_plan(C.c_int(mode), C.c_int(dtype), _i64(a_strides), C.c_int64(int(a_extent)), _i64(idx_strides), _i64(out_shape),
                                         C.c_int(len(out_shape)), C.c_int(int(axis)), C.byref(route), C.byref(launches), oji, C.byref(chunk)))
         return route.value, launches.value, tuple(int(x) for x in oji), chunk.value
+
+    def put_along_axis(self, a: DeviceArray, idx: DeviceArray, values, axis, mode="checked", unique=False):
+        """np.put_along_axis(a, idx, values, axis), in place: a[..., pick(idx[..., j, ...]), ...] = values[..., j, ...]; returns `a`.
+        `a` is a dense DeviceArray; `idx` an int64 DeviceArray of a's rank whose other axes equal a's or are 1; `values` a
+        DeviceArray that broadcasts against idx (over a's other axes) or a Python scalar; both may be views.  Among entries of
+        a line that name the same position the one with the largest j wins.  axis=None flattens a and idx row-major.
+        mode: "checked" (negatives count from the end; an entry outside [-R, R) is dropped and IndexError raised after the
+        launches -- the valid entries have been applied by then), "clip" or "wrap" (fully asynchronous).  unique=True is the
+        caller's promise that no two entries of a line name the same position: one launch, no sort."""
+        return self._scatter_along(SCATTER_PUT, a, idx, values, axis, mode, unique, "put_along_axis")
+
+    def scatter_add(self, a: DeviceArray, idx: DeviceArray, values, axis, mode="checked", unique=False):
+        """np.add.at along an axis (torch's scatter_add_), in place: a[..., pick(idx[..., j, ...]), ...] += values[..., j, ...],
+        the contributions of a destination added one by one in ascending j (f32 in fp64, rounded once); returns `a`.
+        Arguments as put_along_axis()."""
+        return self._scatter_along(SCATTER_ADD, a, idx, values, axis, mode, unique, "scatter_add")
+
+    def put(self, a: DeviceArray, ids: DeviceArray, values, axis=None, mode="checked", unique=False):
+        """The inverse of take(a, ids, axis), in place: a[..., pick(ids[j]), ...] = values[..., j, ...]; returns `a`.  `ids` is a
+        1-D int64 DeviceArray (an N-D one is flattened); `values` has a's shape with `axis` replaced by ids.size, or broadcasts
+        to it, or is a Python scalar.  axis=None indexes a's row-major flattening (np.put).  mode and unique as in put_along_axis()."""
+        return self._scatter_ids(SCATTER_PUT, a, ids, values, axis, mode, unique, "put")
+
+    def index_add(self, a: DeviceArray, ids: DeviceArray, values, axis=None, mode="checked", unique=False):
+        """torch's index_add_ / np.add.at(a, ids, values) along an axis, in place: a[..., pick(ids[j]), ...] += values[..., j, ...]
+        in ascending j; returns `a`.  Arguments as put()."""
+        return self._scatter_ids(SCATTER_ADD, a, ids, values, axis, mode, unique, "index_add")
+
+    def _scatter_target(self, a, idx, values, who):
+        if a.dtype not in DTYPES:
+            raise ValueError(f"{who}: dtype {a.dtype} (f32, f64, i32 and i64 only)")
+        if idx.dtype != np.dtype(np.int64):
+            raise ValueError(f"{who}: the index array must be int64, got {idx.dtype}")
+        if isinstance(values, DeviceArray) and values.dtype != a.dtype:
+            raise ValueError(f"{who}: values are {values.dtype}, the target {a.dtype}")
+        if a is idx or a is values:
+            raise ValueError(f"{who}: the target must not be an operand")
+        if not a.is_dense():
+            raise ValueError(f"{who}: the target must be a dense array (scatter into a dense copy and assign it back)")
+
+    def _scatter_along(self, kind, a, idx, values, axis, mode, unique, who):
+        self._scatter_target(a, idx, values, who)
+        if axis is None:
+            a_flat, idx = self._flat(a), self._flat(idx)
+            if isinstance(values, DeviceArray) and values.size != 1:
+                values = self._flat(values)
+            self._scatter_along(kind, a_flat, idx, values, 0, mode, unique, who)
+            return a
+        if a.ndim != idx.ndim:
+            raise ValueError(f"{who}: the target has rank {a.ndim}, idx rank {idx.ndim}")
+        (axis,) = self._axes(a.ndim, int(axis))
+        si = []
+        for d in range(a.ndim):
+            na, ni = a.shape[d], idx.shape[d]
+            if d != axis and ni != na and ni != 1:
+                raise ValueError(f"{who}: shapes {a.shape} and {idx.shape} do not match at axis {d}")
+            si.append(idx.strides[d] if d == axis or (ni == na and na != 1) else 0)
+        self._scatter(kind, a, a.shape, axis, idx, si, values, idx.shape[axis], mode, unique, who)
+        return a
+
+    def _scatter_ids(self, kind, a, ids, values, axis, mode, unique, who):
+        self._scatter_target(a, ids, values, who)
+        flat = ids if ids.ndim == 1 else self._flat(ids)
+        if axis is None:
+            target, axis = self._flat(a), 0
+        else:
+            target = a
+            (axis,) = self._axes(a.ndim, int(axis))
+        si = [0] * target.ndim
+        si[axis] = flat.strides[0]
+        self._scatter(kind, target, target.shape, axis, flat, si, values, flat.size, mode, unique, who)
+        return a
+
+    def _scatter(self, kind, a, out_shape, axis, idx, si, values, J, mode, unique, who):
+        if mode not in INDEX_MODES:
+            raise ValueError(f"{who}: mode {mode!r} (one of 'checked', 'clip', 'wrap')")
+        nd = len(out_shape)
+        walk = [J if d == axis else out_shape[d] for d in range(nd)]
+        if isinstance(values, DeviceArray):
+            res = self.broadcast(walk, [0] * nd, values.shape, values.strides)
+            if res is None or list(res[0]) != list(walk):
+                raise ValueError(f"{who}: values of shape {values.shape} do not broadcast to {tuple(walk)}")
+            sv = [s if n != 1 else 0 for s, n in zip(res[2], walk)]
+        else:
+            values = self.to_device(np.array([values], dtype=a.dtype))
+            sv = [0] * nd
+        n = int(np.prod(walk, dtype=np.int64))
+        if n and out_shape[axis] == 0:
+            raise IndexError(f"{who}: cannot place entries on an axis of 0 elements")
+        checked = INDEX_MODES[mode] == INDEX_CHECKED and n > 0
+        flag = self.empty((1,), np.int64) if checked else None
+        self._ck(self.c.smhip_scatter_axis(C.c_int(kind), C.c_int(INDEX_MODES[mode]), C.c_int(SCATTER_UNIQUE if unique else 0), C.c_int(DTYPES[a.dtype]),
+                                           C.c_void_p(a.ptr), _i64(out_shape), C.c_int(nd), C.c_int(axis), C.c_void_p(idx.ptr), _i64(si),
+                                           C.c_void_p(values.ptr), _i64(sv), C.c_int64(J), C.c_void_p(flag.ptr if checked else 0)))
+        if checked and int(flag.numpy()[0]):
+            raise IndexError(f"{who}: an index is out of bounds for axis {axis} with size {out_shape[axis]} (the valid entries have been applied)")
+
+    def scatter_raw(self, kind, mode, flags, dtype, out_ptr, out_shape, axis, idx_ptr, idx_strides, val_ptr, val_strides, n_entries, bad_ptr=0, ndim=None):
+        """smhip_scatter_axis with every argument as given (argument-validation tests); ndim defaults to len(out_shape)."""
+        if ndim is None:
+            ndim = len(out_shape) if out_shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        return self.c.smhip_scatter_axis(C.c_int(kind), C.c_int(mode), C.c_int(flags), C.c_int(dtype), C.c_void_p(out_ptr), arr(out_shape), C.c_int(ndim),
+                                         C.c_int(axis), C.c_void_p(idx_ptr), arr(idx_strides), C.c_void_p(val_ptr), arr(val_strides), C.c_int64(n_entries),
+                                         C.c_void_p(bad_ptr))
+
+    def scatter_plan(self, dtype, out_shape, axis, idx_strides, val_strides, n_entries, unique=False, kind=SCATTER_PUT, mode="clip"):
+        """smhip_scatter_plan (host only): (route word, launches, (O, R, J, I), sorted entries) for a call with these strides
+        (elements, against out_shape with `axis` replaced by n_entries)."""
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        mode = INDEX_MODES[mode] if not isinstance(mode, int) else mode
+        route, launches, orji, nsorted = C.c_int(0), C.c_int(0), (C.c_int64 * 4)(), C.c_int64(0)
+        self._ck(self.c.smhip_scatter_plan(C.c_int(kind), C.c_int(mode), C.c_int(SCATTER_UNIQUE if unique else 0), C.c_int(dtype), _i64(out_shape),
+                                           C.c_int(len(out_shape)), C.c_int(int(axis)), _i64(idx_strides), _i64(val_strides), C.c_int64(int(n_entries)),
+                                           C.byref(route), C.byref(launches), orji, C.byref(nsorted)))
+        return route.value, launches.value, tuple(int(x) for x in orji), nsorted.value
 
     def sum(self, a: DeviceArray):
         out = C.c_double(0)

@@ -251,4 +251,13 @@ void take_axis_plan(int dtype, const int64_t *a_strides, int64_t a_extent, const
 int launch_take_axis(int mode, int dtype, const void *a, const int64_t *a_strides, int64_t a_extent, const int64_t *idx, const int64_t *idx_strides,
                      const int64_t *out_shape, int ndim, int axis, void *out, int64_t *bad_out, hipStream_t s);
 
+// scatter_axis.hip: put_along_axis / put / scatter_add / index_add, writing by int64 positions along an axis (smhip_scatter_axis);
+// the checks and the planner are host-only
+int scatter_axis_check(const char *who, int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides,
+                       const int64_t *val_strides, int64_t n_entries);
+void scatter_axis_plan(int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides, const int64_t *val_strides,
+                       int64_t n_entries, int *route, int *launches, int64_t *orji4, int64_t *sorted_entries);
+int launch_scatter_axis(int kind, int mode, int flags, int dtype, void *out, const int64_t *out_shape, int ndim, int axis, const int64_t *idx,
+                        const int64_t *idx_strides, const void *values, const int64_t *val_strides, int64_t n_entries, int64_t *bad_out, hipStream_t s);
+
 }  // namespace smhip

@@ -1571,6 +1571,30 @@ int smhip_take_plan(int mode, int dtype, const int64_t *a_strides, int64_t a_ext
     return SMHIP_OK;
 }
 
+int smhip_scatter_axis(int kind, int mode, int flags, int dtype, void *out, const int64_t *out_shape, int ndim, int axis, const int64_t *idx,
+                       const int64_t *idx_strides, const void *values, const int64_t *val_strides, int64_t n_entries, int64_t *bad_out) {
+    if (int rc = scatter_axis_check("scatter_axis", kind, mode, flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries)) return rc;
+    int64_t n = 1, n_out = 1, walk_shape[SMHIP_MAX_NDIM];
+    for (int d = 0; d < ndim; ++d) walk_shape[d] = d == axis ? n_entries : out_shape[d], n *= walk_shape[d], n_out *= out_shape[d];
+    if (n == 0) return SMHIP_OK;
+    if (!out || !idx || !values) return fail(SMHIP_ERR_INVALID, "scatter_axis: null target, index array or values");
+    const size_t esz = dtype_size(dtype);
+    const Span so{out, (size_t)n_out * esz}, si{idx, span_bytes(walk_shape, idx_strides, ndim, sizeof(int64_t))},
+        sv{values, span_bytes(walk_shape, val_strides, ndim, esz)}, sb{bad_out, bad_out ? sizeof(int64_t) : 0};
+    if (spans_overlap(so, si) || spans_overlap(so, sv) || spans_overlap(so, sb))
+        return fail(SMHIP_ERR_INVALID, "scatter_axis: the target overlaps the index array, the values or bad_out");
+    if (spans_overlap(sb, si) || spans_overlap(sb, sv)) return fail(SMHIP_ERR_INVALID, "scatter_axis: bad_out overlaps the index array or the values");
+    SMHIP_ACQUIRE(s);  // undeclared spans (pooled copies, the sorted lists): ordered behind everything, recorded tiny operators flushed first
+    return launch_scatter_axis(kind, mode, flags, dtype, out, out_shape, ndim, axis, idx, idx_strides, values, val_strides, n_entries, bad_out, s);
+}
+
+int smhip_scatter_plan(int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides,
+                       const int64_t *val_strides, int64_t n_entries, int *route, int *launches, int64_t *orji4, int64_t *sorted_entries) {
+    if (int rc = scatter_axis_check("scatter_plan", kind, mode, flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries)) return rc;
+    scatter_axis_plan(flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries, route, launches, orji4, sorted_entries);
+    return SMHIP_OK;
+}
+
 int smhip_sum(int dtype, const void *a, size_t n, double *out_host) {
     if (!out_host) return fail(SMHIP_ERR_INVALID, "sum: null result");
     void *h = nullptr, *d = nullptr;
