@@ -228,8 +228,12 @@ int smhip_fused_contiguous(int op1, int op2, int dtype, const void *a, const voi
  * element k of scalars_host (n_operands elements of the element type in host memory; entries of array operands are
  * ignored).  operands[0] must be an array.  ops[k] in {ADD, SUB, MUL, DIV}, or POW with a SCALAR x[k+1] and swapped[k] == 0
  * (sm::pow(<expression>, s), UserFunctions.h:42-48: ^2 is a stage of the one-pass kernel, any other exponent cuts the chain and runs
- * smhip_array_scalar's evaluation on the value so far -- the same bits either way).  `out` is dense row-major over `shape` and
- * must not overlap an operand.  Each stage is the single rounded / wrapping operation the separate operator performs, so
+ * smhip_array_scalar's evaluation on the value so far -- the same bits either way).  `out` is dense row-major over `shape`.
+ * It may BE one or more of the operands (out == operands[k]) when each such operand is itself dense row-major over `shape`:
+ * the chain is then evaluated in place (`x = (x - mean) / std`), with the operand's values from before the call.  Any other
+ * overlap of out's n * sizeof(T) bytes with the bytes an operand spans -- an `out` shifted into an operand, `out` equal to a
+ * stepped, transposed or broadcast operand -- is SMHIP_ERR_INVALID, returned before a device is touched.
+ * Each stage is the single rounded / wrapping operation the separate operator performs, so
  * the result is bit-identical to the operator chain.  An operand the one-pass kernel has no index form for (a transposed
  * or stepped view) cuts the chain: that operator runs through smhip_elementwise's kernels, the rest stays fused. */
 #define SMHIP_CHAIN_MAX_OPERANDS 16

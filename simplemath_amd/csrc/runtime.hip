@@ -1352,7 +1352,7 @@ int smhip_fused_expr_bcast(const char *hip_expression, int dtype, const void *co
 namespace {
 // What smhip_chain and smhip_chain_sum check alike; *n_out = the result's element count.
 int check_chain(const char *who, int dtype, int n_operands, const void *const *operands, const int64_t *strides, const void *scalars_host,
-                const int *ops, const int *swapped, const int64_t *shape, int ndim, int64_t *n_out) {
+                const int *ops, const int *swapped, const int64_t *shape, int ndim, const void *out, int64_t *n_out) {
     if (!valid_dtype(dtype)) return fail(SMHIP_ERR_INVALID, "%s: bad dtype %d", who, dtype);
     if (n_operands < 2 || n_operands > SMHIP_CHAIN_MAX_OPERANDS) return fail(SMHIP_ERR_INVALID, "%s: %d operands outside 2..%d", who, n_operands, SMHIP_CHAIN_MAX_OPERANDS);
     if (ndim < 1 || ndim > SMHIP_MAX_NDIM) return fail(SMHIP_ERR_INVALID, "%s: ndim %d outside 1..%d", who, ndim, SMHIP_MAX_NDIM);
@@ -1371,6 +1371,20 @@ int check_chain(const char *who, int dtype, int n_operands, const void *const *o
         }
         for (int i = 0; i < ndim; ++i)
             if (strides[(size_t)k * ndim + i] < 0) return fail(SMHIP_ERR_INVALID, "%s: negative stride (operand %d, dim %d)", who, k, i);
+    }
+    // In place is the one overlap a chain can take: `out` IS an operand, and that operand is dense row-major over `shape` (a stage
+    // reads element i of it before anything writes element i; a segment that is not the chain's last goes to a temporary).
+    const Span so{out, out ? (size_t)n * dtype_size(dtype) : 0};
+    for (int k = 0; k < n_operands; ++k) {
+        if (!operands[k] || !spans_overlap(Span{operands[k], span_bytes(shape, strides + (size_t)k * ndim, ndim, dtype_size(dtype))}, so)) continue;
+        bool in_place = operands[k] == out;
+        int64_t acc = 1;
+        for (int i = ndim; in_place && i-- > 0;) {
+            if (shape[i] != 1 && strides[(size_t)k * ndim + i] != acc) in_place = false;
+            acc *= shape[i];
+        }
+        if (!in_place)
+            return fail(SMHIP_ERR_INVALID, "%s: the result overlaps operand %d (only out == an operand that is dense over the result's shape is allowed)", who, k);
     }
     for (int k = 0; k + 1 < n_operands; ++k) {
         if (ops[k] == SMHIP_OP_POW) {  // r ^ scalar only: sm::pow(<expression>, s)
@@ -1393,7 +1407,7 @@ int check_chain(const char *who, int dtype, int n_operands, const void *const *o
 int smhip_chain(int dtype, int n_operands, const void *const *operands, const int64_t *strides, const void *scalars_host, const int *ops,
                 const int *swapped, const int64_t *shape, int ndim, void *out) {
     int64_t n;
-    if (int rc = check_chain("chain", dtype, n_operands, operands, strides, scalars_host, ops, swapped, shape, ndim, &n)) return rc;
+    if (int rc = check_chain("chain", dtype, n_operands, operands, strides, scalars_host, ops, swapped, shape, ndim, out, &n)) return rc;
     if (n == 0) return SMHIP_OK;
     if (!out) return fail(SMHIP_ERR_INVALID, "chain: null output");
     Span reads[SMHIP_CHAIN_MAX_OPERANDS];
@@ -1408,7 +1422,7 @@ int smhip_chain(int dtype, int n_operands, const void *const *operands, const in
 int smhip_chain_sum_async(int dtype, int n_operands, const void *const *operands, const int64_t *strides, const void *scalars_host,
                           const int *ops, const int *swapped, const int64_t *shape, int ndim, double *sum_dev) {
     int64_t n;
-    if (int rc = check_chain("chain_sum", dtype, n_operands, operands, strides, scalars_host, ops, swapped, shape, ndim, &n)) return rc;
+    if (int rc = check_chain("chain_sum", dtype, n_operands, operands, strides, scalars_host, ops, swapped, shape, ndim, nullptr, &n)) return rc;
     if (!sum_dev) return fail(SMHIP_ERR_INVALID, "chain_sum: null result");
     if (n == 0) return fail(SMHIP_ERR_INVALID, "chain_sum: empty shape");
     SMHIP_ACQUIRE(s);  // a reduction: undeclared spans, ordered behind everything (like smhip_sum_async)

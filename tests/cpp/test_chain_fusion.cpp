@@ -185,6 +185,64 @@ static void host_values() {
         }
 }
 
+// `x = <expression that reads x>`: evaluated straight into x (Chain::may_write_into: x is dense and every operand in x's storage is
+// exactly x), also where the stage that writes runs ALONE -- behind a transposed operand, log, the f64 exp, a general pow, a second
+// row, a fifth dense operand.  Expected: the same right-hand side bound to a fresh value BEFORE the assignment.
+template <typename T>
+static void in_place_statements() {
+    const std::size_t n = 96;
+    const auto B = random_array<T>(n, n), y = random_array<T>(n, n), m = random_array<T>(n, 1), row = random_array<T>(1, n), row2 = random_array<T>(1, n);
+    const auto d1 = random_array<T>(n, n), d2 = random_array<T>(n, n), d3 = random_array<T>(n, n), d4 = random_array<T>(n, n);
+    const auto x0 = random_array<T>(n, n);
+    auto direct = [] { return sm::fusion_stats().direct_assignments; };
+#define IN_PLACE(EXPR)                                      \
+    do {                                                    \
+        auto x = x0 + T(0);                                 \
+        auto want = (EXPR);                                 \
+        const auto before = direct();                       \
+        x = (EXPR);                                         \
+        CHECK(direct() == before + 1);                      \
+        CHECK(same_bits(x, want));                          \
+    } while (0)
+    IN_PLACE(B.transpose() + x);                 // the one operator runs through the transposed-operand tile kernel, its output an operand
+    IN_PLACE(x - B.transpose());
+    IN_PLACE((x * m + y) - B.transpose());       // ... behind a fused segment
+    IN_PLACE(sm::exp(x - m));                    // f32: one pass; f64: the subtraction into a temporary, exp from there into x
+    IN_PLACE(sm::log(x * x + T(1)));
+    IN_PLACE(sm::pow(x + y, T(2.5)));
+    IN_PLACE(row + x);
+    IN_PLACE((row + row2) * x);                  // two rows at the start: that operator runs alone
+    IN_PLACE((x * row + row2) - x);              // the second row cuts the chain before the stage that reads x again
+    IN_PLACE((((B + y) * d1 - d2) / d3 + d4) + x);   // six distinct dense operands: x is read behind the cut
+    IN_PLACE((((x + y) * d1 - d2) / d3 + d4) * B);   // ... and before it
+#undef IN_PLACE
+    {   // a dense block of rows, read and written
+        auto x = x0 + T(0);
+        auto want = sm::sqrt(sm::abs(x(SLICE(2, 5), SLICE_ALL) - y(SLICE(2, 5), SLICE_ALL)));
+        const auto keep = x + T(0);
+        const auto before = direct();
+        x(SLICE(2, 5), SLICE_ALL) = sm::sqrt(sm::abs(x(SLICE(2, 5), SLICE_ALL) - y(SLICE(2, 5), SLICE_ALL)));
+        CHECK(direct() == before + 1);
+        auto got = x(SLICE(2, 5), SLICE_ALL) + T(0);
+        CHECK(same_bits(got, want));
+        auto above = x(SLICE(0, 2), SLICE_ALL) + T(0), above0 = keep(SLICE(0, 2), SLICE_ALL) + T(0);
+        auto below = x(SLICE(5, n), SLICE_ALL) + T(0), below0 = keep(SLICE(5, n), SLICE_ALL) + T(0);
+        CHECK(same_bits(above, above0) && same_bits(below, below0));
+    }
+    {   // NOT in place: x is read through another view of its own storage
+        auto x = x0 + T(0);
+        auto want = x.transpose() + x;
+        const auto before = direct();
+        x = x.transpose() + x;
+        CHECK(direct() == before);
+        CHECK(same_bits(x, want));
+        auto want2 = sm::exp(x - x(SLICE_ALL, SLICE(0, 1)));
+        x = sm::exp(x - x(SLICE_ALL, SLICE(0, 1)));
+        CHECK(direct() == before);
+        CHECK(same_bits(x, want2));
+    }
+}
+
 static void ordering() {
     const std::size_t n = 1 << 16;
     // a host write between two statements: the first statement's value was computed at its `;`
@@ -250,6 +308,8 @@ static void ordering() {
     auto m = p + p;
     auto m2 = std::move(m) * 2.0f + p;
     CHECK(m2(1, 1) == 5.0f);
+    in_place_statements<float>();
+    in_place_statements<double>();
 }
 
 // sm::pow of an expression's temporary is one more stage of its chain: ^2 inside the kernel, any other exponent by cutting the chain
