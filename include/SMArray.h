@@ -65,6 +65,12 @@ enum class index_mode {
     wrap = SMHIP_INDEX_WRAP,        // the non-negative remainder mod R (np.take(mode="wrap")): fully asynchronous
 };
 
+// Which of equal edges sm::searchsorted names (smhip.h: smhip_side): np.searchsorted's side.
+enum class side {
+    left = SMHIP_SIDE_LEFT,    // the first i with !(edges[i] before x): a value equal to an edge stands AT the edge's first copy
+    right = SMHIP_SIDE_RIGHT,  // the first i with x before edges[i]: it stands AFTER the edge's last copy
+};
+
 namespace detail {
 
 // ---- deferred operator chains ------------------------------------------------------------------------------------------
@@ -102,6 +108,7 @@ struct FusionStats {
     unsigned long long sorts = 0;               // smhip_sort_axis calls: sort / argsort / sort_with_index and their _flat forms
     unsigned long long takes = 0;               // smhip_take_axis calls: take / take_along_axis / take_flat
     unsigned long long scatters = 0;            // smhip_scatter_axis calls: put_along_axis / put / put_flat / scatter_add / index_add
+    unsigned long long counts = 0;              // smhip_searchsorted / smhip_bincount / smhip_histogram calls
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -913,6 +920,80 @@ public:
         return scatter_ids(SMHIP_SCATTER_ADD, ids, nullptr, value, axis, mode, unique);
     }
 
+    // COUNTING (np.searchsorted, np.bincount, np.histogram).  The results are SMArray<std::int64_t>, resident on the device, and
+    // feed the next chain like any array.  Values are ordered as sort() orders them ascending: -0 == +0, every NaN after every
+    // number, NaNs equal among themselves.
+    //   edges.searchsorted(x, side)   *this is the 1-D table of edges, sorted ascending; the result has x's shape and holds, for
+    //                                 every element of x, the first i with !(edges[i] before x) (side::left) or the first i with
+    //                                 x before edges[i] (side::right), in [0, edges.size()].
+    //   ids.bincount(nbins, mode)     *this holds int or std::int64_t ids, read row-major; result[p] = how many of them name position
+    //                                 p of nbins.  The same bits as index_add of 1 onto nbins zeros, in every mode.  checked (the
+    //                                 default): negatives count from the end, an id outside [-nbins, nbins) is DROPPED and, after the
+    //                                 flag word is downloaded -- a stream synchronisation --, std::out_of_range is thrown; clip and wrap
+    //                                 never wait.  The length is never inferred from the data: write sm::max of the ids if you want it.
+    //   x.histogram(bins, lo, hi)     {counts, edges} of `bins` equal bins over [lo, hi] (float and double): np.histogram(x, bins,
+    //                                 range=(lo, hi)), with numpy's own edges, np.linspace(lo, hi, bins + 1) rounded to T, computed on
+    //                                 the host and uploaded.  lo == hi stands for (lo - 0.5, hi + 0.5).
+    //   x.histogram(edges)            counts between explicit edges (1-D, non-decreasing, at least two; any of the four types).
+    //                                 The bin of a value is searchsorted(edges, v, side::right) - 1; a value equal to the last edge
+    //                                 goes to the last bin; values outside the edges and NaNs are not counted.
+    // Integer counts are summed with atomic adds: integer addition commutes, so every run gives the same bits.  Operands may be
+    // views (copied dense first) or pending chains (evaluated first).  std::invalid_argument: 0 bins with entries to count, a
+    // negative count, a table that is not 1-D, and where numpy raises for a range -- bins < 1, lo or hi not finite, lo > hi, edges
+    // that do not increase once rounded to T.  Each is ONE library call (sm::fusion_stats().counts).
+    SMArray<std::int64_t> searchsorted(const SMArray &x, side s = side::left) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "searchsorted: f32, f64, i32 and i64");
+        if (_shape.size() != 1) throw std::invalid_argument("simpleMath/MI355X: searchsorted: the edges must be 1-D");
+        hip::DeviceGuard on(common_device(*this, x));
+        std::unique_ptr<SMArray> holder;
+        const T *edges = dense_device(holder);
+        const T *in = x.device_data();  // a pending chain that produces the operand runs here
+        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>(x._shape));
+        if (out.totalSize == 0) return out;
+        const auto sh = hip::to_i64(x._shape), st = hip::to_i64(x._strides);
+        hip::check(smhip_searchsorted(static_cast<int>(s), hip::dtype_of<T>::id, edges, static_cast<std::int64_t>(totalSize), in, sh.data(), st.data(),
+                                      static_cast<int>(sh.size()), out.device_data_mut()));
+        ++detail::tls_fusion_stats.counts;
+        return out;
+    }
+    SMArray<std::int64_t> bincount(std::int64_t nbins, index_mode mode = index_mode::checked) const {
+        static_assert(std::is_same_v<T, int> || std::is_same_v<T, std::int64_t>, "bincount: the ids are int or std::int64_t");
+        if (nbins < 0 || (nbins == 0 && totalSize != 0))
+            throw std::invalid_argument("simpleMath/MI355X: bincount: cannot count " + std::to_string(totalSize) + " ids into " + std::to_string(nbins) + " bins");
+        hip::DeviceGuard on(device());
+        const T *ids = device_data();  // a pending chain that produces the ids runs here
+        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{static_cast<std::size_t>(nbins)});
+        if (nbins == 0) return out;
+        const bool checked = mode == index_mode::checked && totalSize != 0;
+        hip::DeviceBuffer flag;  // one word from the pool, only when someone will read it
+        if (checked) flag = hip::DeviceBuffer(sizeof(std::int64_t));
+        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
+        hip::check(smhip_bincount(static_cast<int>(mode), hip::dtype_of<T>::id, ids, sh.data(), st.data(), static_cast<int>(sh.size()), nbins,
+                                  out.device_data_mut(), flag.template as<std::int64_t>()));
+        ++detail::tls_fusion_stats.counts;
+        if (checked) {
+            std::int64_t bad = 0;
+            hip::check(smhip_download(&bad, flag.get(), sizeof bad));  // waits for the stream
+            if (bad) throw std::out_of_range("simpleMath/MI355X: bincount: an id is out of bounds for " + std::to_string(nbins) + " bins");
+        }
+        return out;
+    }
+    std::pair<SMArray<std::int64_t>, SMArray> histogram(std::int64_t bins, double lo, double hi) const {
+        static_assert(std::is_floating_point_v<T>, "histogram over a range: float and double");
+        std::unique_ptr<T[]> table(bins >= 1 ? new T[static_cast<std::size_t>(bins) + 1] : nullptr);
+        const int rc = smhip_histogram_edges(hip::dtype_of<T>::id, bins, lo, hi, table.get());
+        if (rc == SMHIP_ERR_INVALID) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + smhip_last_error());
+        hip::check(rc);
+        SMArray edges(table.release(), std::vector<std::size_t>{static_cast<std::size_t>(bins) + 1});
+        SMArray<std::int64_t> counts = count_between(edges, SMHIP_HISTOGRAM_UNIFORM, lo, hi);
+        return {std::move(counts), std::move(edges)};
+    }
+    SMArray<std::int64_t> histogram(const SMArray &edges) const {
+        if (edges._shape.size() != 1 || edges.totalSize < 2)
+            throw std::invalid_argument("simpleMath/MI355X: histogram: the edges must be 1-D and at least two");
+        return count_between(edges, 0, 0.0, 0.0);
+    }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -1401,6 +1482,22 @@ private:
                                         " elements (the valid entries have been applied)");
         }
         return *this;
+    }
+
+    // counts of this array's values between `edges` (1-D, bins + 1 of them); flags / lo / hi as smhip_histogram takes them.
+    SMArray<std::int64_t> count_between(const SMArray &edges, int flags, double lo, double hi) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "histogram: f32, f64, i32 and i64");
+        hip::DeviceGuard on(common_device(*this, edges));
+        std::unique_ptr<SMArray> holder;
+        const T *table = edges.dense_device(holder);
+        const T *in = device_data();  // a pending chain that produces the operand runs here
+        const std::size_t bins = edges.totalSize - 1;
+        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{bins});
+        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
+        hip::check(smhip_histogram(flags, hip::dtype_of<T>::id, in, sh.data(), st.data(), static_cast<int>(sh.size()), table, static_cast<std::int64_t>(bins), lo, hi,
+                                   out.device_data_mut()));
+        ++detail::tls_fusion_stats.counts;
+        return out;
     }
 
     // Device pointer to a dense version of this array (itself when already dense).

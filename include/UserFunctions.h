@@ -328,6 +328,20 @@ SMArray<T> &index_add(SMArray<T> &arr, const SMArray<std::int64_t> &ids, const V
     return arr.index_add(ids, values, axis, mode, unique);
 }
 
+// Counting (np.searchsorted, np.bincount, np.histogram); the results are SMArray<std::int64_t> on the device.  searchsorted: for every
+// element of x its place among the ascending 1-D `edges` (side::left: at an equal edge's first copy, side::right: after its last).
+// bincount: how many of the int / std::int64_t `ids` name each of nbins positions, the same bits as index_add of 1 onto zeros in every
+// mode.  histogram(x, bins, lo, hi): {counts, edges} of equal bins over [lo, hi], numpy's edges; histogram(x, edges): counts between
+// explicit edges.  Semantics as the members of the same names (SMArray.h) and smhip_searchsorted / smhip_bincount / smhip_histogram.
+template <typename T>
+SMArray<std::int64_t> searchsorted(const SMArray<T> &edges, const SMArray<T> &x, side s = side::left) { return edges.searchsorted(x, s); }
+template <typename T>
+SMArray<std::int64_t> bincount(const SMArray<T> &ids, std::int64_t nbins, index_mode mode = index_mode::checked) { return ids.bincount(nbins, mode); }
+template <typename T>
+std::pair<SMArray<std::int64_t>, SMArray<T>> histogram(const SMArray<T> &x, std::int64_t bins, double lo, double hi) { return x.histogram(bins, lo, hi); }
+template <typename T>
+SMArray<std::int64_t> histogram(const SMArray<T> &x, const SMArray<T> &edges) { return x.histogram(edges); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

@@ -536,6 +536,66 @@ int smhip_scatter_plan(int kind, int mode, int flags, int dtype, const int64_t *
                        const int64_t *idx_strides, const int64_t *val_strides, int64_t n_entries,
                        int *route, int *launches, int64_t *orji4, int64_t *sorted_entries);
 
+/* ------------------------------------------ searchsorted / bincount / histogram */
+/* Counting.  The results are int64_t and resident on the device.  The contract:
+ *   order        of values: smhip_sort_axis's ASCENDING order.  a is BEFORE b when a < b, or when b is a NaN and a is not: -0.0 == +0.0,
+ *                every NaN stands after every number, NaNs are equal among themselves.
+ *   searchsorted np.searchsorted(edges, x, side): for E edges, sorted as smhip_sort_axis sorts ascending (trailing NaNs allowed),
+ *                  LEFT   the first i with !(edges[i] before x)
+ *                  RIGHT  the first i with  x before edges[i]
+ *                in [0, E]; E = 0 gives zeros.  edges and x have the same element type, so every comparison is exact.  Unsorted
+ *                edges are a broken precondition and are not checked: the result is then some value in [0, E] (the search is a
+ *                loop of at most ceil(log2(E + 1)) steps whatever the table holds).
+ *   bincount     counts[p] = the number of ids that name position p of nbins, the ids (i32 or i64, any shape) read row-major.  Equal
+ *                bit for bit, in every mode, to smhip_scatter_axis(ADD) of the int64 constant 1 onto nbins zeros: smhip_index_mode
+ *                as there -- CLIP and WRAP as in smhip_take_axis; CHECKED: a negative id counts from the end, an id outside
+ *                [-nbins, nbins) is DROPPED and, with bad_out given, any lane that meets one stores the constant 1 there (the library
+ *                sets *bad_out to 0 in stream order first).  The length is never inferred from the data.
+ *   histogram    np.histogram(x, bins=edges): for bins + 1 edges, the bin of a value is searchsorted(edges, v, RIGHT) - 1; a value
+ *                equal to the last edge goes to the last bin; values before the first edge, after the last one, and NaNs are not
+ *                counted; repeated edges give empty bins.  x and the edges have the same element type.  With
+ *                SMHIP_HISTOGRAM_UNIFORM (f32 and f64) the table is the one smhip_histogram_edges makes for (bins, lo, hi) and the
+ *                bin is found from one fp64 multiply, (v - lo) * bins / (hi - lo), corrected against the table: the same counts, less
+ *                searching.  The kernel never recomputes an edge.
+ *   safety       in no mode is an address outside the result formed: an id is a position in [0, nbins - 1] before it is used as one.
+ *   determinism  INTEGER COUNTS USE ATOMIC ADDS (in LDS; on the result's words when bins > K).  Integer addition commutes, so the
+ *                counts are the same bits on every run, stream and grid whatever order the increments arrive in.
+ * `x` / `ids` is any view (strides in ELEMENTS, >= 0, rank 1 .. SMHIP_MAX_NDIM); one that is not dense row-major is copied dense
+ * first.  Checked before any device is touched (SMHIP_ERR_INVALID): side, mode, flags, dtype, ndim, negative extents or strides, null
+ * shape / strides, a negative count of bins or edges, 0 bins with entries to count, spans past 2^59 elements, null pointers where
+ * there is something to read or write, pointers that are not aligned to their element, a result overlapping an operand, the table or
+ * bad_out; for SMHIP_HISTOGRAM_UNIFORM also bins < 1, a range that is not finite and lo > hi.  No elements: searchsorted is a no-op,
+ * the other two write zeros.  Asynchronous, stream-ordered; recorded tiny operators are flushed first. */
+typedef enum smhip_side { SMHIP_SIDE_LEFT = 0, SMHIP_SIDE_RIGHT = 1 } smhip_side;
+typedef enum smhip_count_op { SMHIP_COUNT_SEARCHSORTED = 0, SMHIP_COUNT_BINCOUNT = 1, SMHIP_COUNT_HISTOGRAM = 2 } smhip_count_op;
+#define SMHIP_HISTOGRAM_UNIFORM 1 /* smhip_histogram's flag: edges_dev is the uniform table of (bins, lo, hi) */
+/* out: dense row-major over `shape`, one int64_t per element of x.  edges: n_edges elements in device memory. */
+int smhip_searchsorted(int side, int dtype, const void *edges, int64_t n_edges,
+                       const void *x, const int64_t *shape, const int64_t *strides, int ndim, int64_t *out);
+/* counts: nbins int64_t in device memory, overwritten.  bad_out_or_null: one int64_t in device memory. */
+int smhip_bincount(int mode, int ids_dtype, const void *ids, const int64_t *shape, const int64_t *strides, int ndim,
+                   int64_t nbins, int64_t *counts, int64_t *bad_out_or_null);
+/* edges_dev: bins + 1 elements of x's type in device memory; counts: bins int64_t, overwritten.  lo / hi are read only with
+ * SMHIP_HISTOGRAM_UNIFORM, and must then be the range the table was made for. */
+int smhip_histogram(int flags, int dtype, const void *x, const int64_t *shape, const int64_t *strides, int ndim,
+                    const void *edges_dev, int64_t bins, double lo, double hi, int64_t *counts);
+/* Host only, no device touched: the uniform table, np.linspace(lo, hi, bins + 1).astype(T) bit for bit -- lo + i * ((hi - lo) / bins)
+ * in fp64 with the product rounded before the sum, the last edge hi itself, each rounded to f32 or f64 -- into bins + 1 elements of
+ * HOST memory.  lo == hi stands for (lo - 0.5, hi + 0.5), as in numpy.  SMHIP_ERR_INVALID where numpy raises: bins < 1, lo or hi not
+ * finite, lo > hi, rounded edges that are not strictly increasing ("too many bins for the range"). */
+int smhip_histogram_edges(int dtype, int64_t bins, double lo, double hi, void *edges_host);
+/* Host only, no device touched: the route a call would take.  `what` is an smhip_count_op, `flags` smhip_histogram's, `bins` the
+ * number of edges for SEARCHSORTED and of bins otherwise.  *route = SMHIP_COUNT_ROUTE_* ORed with the flag below; *launches = the
+ * kernel launches of the call (memsets are not launches); info6 = {workgroups, the entries of a workgroup's slice at most (below 2^32
+ * on the counting routes: a 32-bit counter cannot wrap), replicas of each LDS counter, K = the most bins route LDS takes, the most
+ * edges of this element type that are staged in LDS, 1 when this call's table is staged}.  Any output may be NULL. */
+#define SMHIP_COUNT_ROUTE_NONE 0   /* nothing to launch: no elements, or no edges */
+#define SMHIP_COUNT_ROUTE_LDS 1    /* counting: bins <= K, counters in LDS, rows summed by a finishing launch; searchsorted: the edges in LDS */
+#define SMHIP_COUNT_ROUTE_GLOBAL 2 /* counting: bins > K, atomic adds on the cleared result; searchsorted: the edges searched in global memory */
+#define SMHIP_COUNT_COPY 0x100     /* the operand is not dense row-major and is copied dense first (one launch) */
+int smhip_count_plan(int what, int flags, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins,
+                     int *route, int *launches, int64_t *info6);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

@@ -62,6 +62,14 @@ SCATTER_UNIQUE = 1                   # smhip_scatter_axis's flag: no two entries
 # smhip_scatter_plan's route word: a kernel id in the low byte, the flag above it
 SCATTER_ROUTE_NONE, SCATTER_ROUTE_DIRECT, SCATTER_ROUTE_ROWS, SCATTER_ROUTE_SORTED, SCATTER_ROUTE_SORTED_ROWS = range(5)
 SCATTER_COPY = 0x100
+SIDE_LEFT, SIDE_RIGHT = range(2)  # smhip_side
+SIDES = {"left": SIDE_LEFT, "right": SIDE_RIGHT}
+COUNT_SEARCHSORTED, COUNT_BINCOUNT, COUNT_HISTOGRAM = range(3)  # smhip_count_op
+COUNT_OPS = {"searchsorted": COUNT_SEARCHSORTED, "bincount": COUNT_BINCOUNT, "histogram": COUNT_HISTOGRAM}
+HISTOGRAM_UNIFORM = 1  # smhip_histogram's flag: the table is the uniform one of (bins, lo, hi)
+# smhip_count_plan's route word: a route in the low byte, the flag above it
+COUNT_ROUTE_NONE, COUNT_ROUTE_LDS, COUNT_ROUTE_GLOBAL = range(3)
+COUNT_COPY = 0x100
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -950,6 +958,125 @@ class Smhip:
                                            C.c_int(len(out_shape)), C.c_int(int(axis)), _i64(idx_strides), _i64(val_strides), C.c_int64(int(n_entries)),
                                            C.byref(route), C.byref(launches), orji, C.byref(nsorted)))
         return route.value, launches.value, tuple(int(x) for x in orji), nsorted.value
+
+    # -- counting -------------------------------------------------------------------
+    def searchsorted(self, edges: DeviceArray, x: DeviceArray, side="left", out: DeviceArray | None = None):
+        """np.searchsorted(edges, x, side) -> an int64 DeviceArray of x's shape (or into `out`, a dense int64 array of x's element
+        count).  `edges` is a 1-D dense DeviceArray of x's dtype, sorted ascending as sort() sorts (NaNs last); `x` any view."""
+        if side not in SIDES:
+            raise ValueError(f"searchsorted: side {side!r} (one of 'left', 'right')")
+        if x.dtype not in DTYPES or edges.dtype != x.dtype:
+            raise ValueError(f"searchsorted: edges are {edges.dtype}, x {x.dtype} (the same one of f32, f64, i32, i64)")
+        if edges.ndim != 1 or not edges.is_dense():
+            raise ValueError("searchsorted: the edges must be a dense 1-D array")
+        if out is None:
+            out = self.empty(x.shape, np.int64)
+        elif out is x or out is edges:
+            raise ValueError("searchsorted: out must not be an operand")
+        elif out.dtype != np.dtype(np.int64) or out.size != x.size or not out.is_dense():
+            raise ValueError(f"searchsorted: out must be a dense int64 array of {x.size} elements; got {out.dtype} {out.shape} dense={out.is_dense()}")
+        self._ck(self.c.smhip_searchsorted(C.c_int(SIDES[side]), C.c_int(DTYPES[x.dtype]), C.c_void_p(edges.ptr), C.c_int64(edges.size), C.c_void_p(x.ptr),
+                                           _i64(x.shape), _i64(x.strides), C.c_int(x.ndim), C.c_void_p(out.ptr)))
+        return out
+
+    def bincount(self, ids: DeviceArray, nbins, mode="checked"):
+        """counts[p] = how many of `ids` (an int32 or int64 DeviceArray, any view, read row-major) name position p of `nbins` -> an
+        int64 DeviceArray of shape (nbins,).  The same bits as index_add(zeros, ids, 1, 0, mode).  mode: "checked" (negatives count
+        from the end; an id outside [-nbins, nbins) is dropped and IndexError raised after the launches -- the valid ids have been
+        counted by then), "clip" or "wrap" (fully asynchronous).  The length is never inferred from the data."""
+        if mode not in INDEX_MODES:
+            raise ValueError(f"bincount: mode {mode!r} (one of 'checked', 'clip', 'wrap')")
+        if ids.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise ValueError(f"bincount: the ids must be int32 or int64, got {ids.dtype}")
+        nbins = int(nbins)
+        if nbins < 0 or (nbins == 0 and ids.size):
+            raise ValueError(f"bincount: cannot count {ids.size} ids into {nbins} bins")
+        counts = self.empty((nbins,), np.int64)
+        checked = INDEX_MODES[mode] == INDEX_CHECKED and ids.size > 0
+        flag = self.empty((1,), np.int64) if checked else None
+        self._ck(self.c.smhip_bincount(C.c_int(INDEX_MODES[mode]), C.c_int(DTYPES[ids.dtype]), C.c_void_p(ids.ptr), _i64(ids.shape), _i64(ids.strides),
+                                       C.c_int(ids.ndim), C.c_int64(nbins), C.c_void_p(counts.ptr), C.c_void_p(flag.ptr if checked else 0)))
+        if checked and int(flag.numpy()[0]):
+            raise IndexError(f"bincount: an id is out of bounds for {nbins} bins (the valid ids have been counted)")
+        return counts
+
+    def bincount_raw(self, mode, dtype, ids_ptr, shape, strides, nbins, counts_ptr, bad_ptr=0, ndim=None):
+        """smhip_bincount with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        return self.c.smhip_bincount(C.c_int(mode), C.c_int(dtype), C.c_void_p(ids_ptr), arr(shape), arr(strides), C.c_int(ndim), C.c_int64(nbins),
+                                     C.c_void_p(counts_ptr), C.c_void_p(bad_ptr))
+
+    def searchsorted_raw(self, side, dtype, edges_ptr, n_edges, x_ptr, shape, strides, out_ptr, ndim=None):
+        """smhip_searchsorted with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        return self.c.smhip_searchsorted(C.c_int(side), C.c_int(dtype), C.c_void_p(edges_ptr), C.c_int64(n_edges), C.c_void_p(x_ptr), arr(shape), arr(strides),
+                                         C.c_int(ndim), C.c_void_p(out_ptr))
+
+    def histogram_raw(self, flags, dtype, x_ptr, shape, strides, edges_ptr, bins, lo, hi, counts_ptr, ndim=None):
+        """smhip_histogram with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        return self.c.smhip_histogram(C.c_int(flags), C.c_int(dtype), C.c_void_p(x_ptr), arr(shape), arr(strides), C.c_int(ndim), C.c_void_p(edges_ptr),
+                                      C.c_int64(bins), C.c_double(lo), C.c_double(hi), C.c_void_p(counts_ptr))
+
+    def histogram_edges(self, bins, lo, hi, dtype):
+        """smhip_histogram_edges (host only): np.linspace(lo, hi, bins + 1).astype(dtype) bit for bit, as a numpy array; ValueError
+        where np.histogram(..., bins, range=(lo, hi)) raises."""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"histogram: a range needs float32 or float64 values, got {dtype}")
+        bins = int(bins)
+        edges = np.empty(max(bins, 0) + 1, dtype)
+        rc = self.c.smhip_histogram_edges(C.c_int(DTYPES[dtype]), C.c_int64(bins), C.c_double(lo), C.c_double(hi), edges.ctypes.data_as(C.c_void_p))
+        if rc == ERR_INVALID:
+            raise ValueError(self.c.smhip_last_error().decode())
+        self._ck(rc)
+        return edges
+
+    def histogram(self, x: DeviceArray, bins, range=None):
+        """np.histogram.  histogram(x, bins, range=(lo, hi)) -> (counts, edges): `bins` equal bins over [lo, hi] for float32 / float64
+        x; the edges are numpy's, as a DeviceArray of x's dtype.  histogram(x, edges) with `edges` a dense 1-D DeviceArray of x's
+        dtype (f32, f64, i32, i64; non-decreasing, at least 2) -> counts.  counts is an int64 DeviceArray of shape (bins,); x is any
+        view, read row-major.  The bin of a value is searchsorted(edges, v, "right") - 1, the last edge belongs to the last bin,
+        values outside the edges and NaNs are not counted."""
+        if x.dtype not in DTYPES:
+            raise ValueError(f"histogram: dtype {x.dtype} (f32, f64, i32 and i64 only)")
+        if isinstance(bins, DeviceArray):
+            if range is not None:
+                raise ValueError("histogram: explicit edges take no range")
+            edges = bins
+            if edges.dtype != x.dtype or edges.ndim != 1 or not edges.is_dense() or edges.size < 2:
+                raise ValueError(f"histogram: the edges must be a dense 1-D {x.dtype} array of at least 2 elements")
+            flags, nb, lo, hi, result = 0, edges.size - 1, 0.0, 0.0, None
+        else:
+            if range is None:
+                raise ValueError("histogram: equal bins need range=(lo, hi) (the range is never inferred from the data)")
+            lo, hi = float(range[0]), float(range[1])
+            edges = self.to_device(self.histogram_edges(bins, lo, hi, x.dtype))
+            flags, nb, result = HISTOGRAM_UNIFORM, int(bins), edges
+        counts = self.empty((nb,), np.int64)
+        self._ck(self.c.smhip_histogram(C.c_int(flags), C.c_int(DTYPES[x.dtype]), C.c_void_p(x.ptr), _i64(x.shape), _i64(x.strides), C.c_int(x.ndim),
+                                        C.c_void_p(edges.ptr), C.c_int64(nb), C.c_double(lo), C.c_double(hi), C.c_void_p(counts.ptr)))
+        return counts if result is None else (counts, result)
+
+    def count_plan(self, what, dtype, shape, strides, bins, uniform=False, ndim=None):
+        """smhip_count_plan (host only): (route word, launches, (workgroups, entries per slice, replicas, K, edges staged at most,
+        staged)) for `what` ("searchsorted", "bincount", "histogram") over a view of these shape and strides (elements); `bins` is
+        the number of edges for searchsorted, of bins otherwise."""
+        what = COUNT_OPS[what] if not isinstance(what, int) else what
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        route, launches, info = C.c_int(0), C.c_int(0), (C.c_int64 * 6)()
+        self._ck(self.c.smhip_count_plan(C.c_int(what), C.c_int(HISTOGRAM_UNIFORM if uniform else 0), C.c_int(dtype), arr(shape), arr(strides), C.c_int(ndim),
+                                         C.c_int64(int(bins)), C.byref(route), C.byref(launches), info))
+        return route.value, launches.value, tuple(int(v) for v in info)
 
     def sum(self, a: DeviceArray):
         out = C.c_double(0)

@@ -260,4 +260,17 @@ void scatter_axis_plan(int flags, int dtype, const int64_t *out_shape, int ndim,
 int launch_scatter_axis(int kind, int mode, int flags, int dtype, void *out, const int64_t *out_shape, int ndim, int axis, const int64_t *idx,
                         const int64_t *idx_strides, const void *values, const int64_t *val_strides, int64_t n_entries, int64_t *bad_out, hipStream_t s);
 
+// count.hip: searchsorted, bincount and histogram (smhip_searchsorted / smhip_bincount / smhip_histogram); the checks, the planner and
+// the uniform edge table are host-only.  `what` is an smhip_count_op; `bins` the edges of searchsorted, the bins of the other two.
+int count_check(const char *who, int what, int flags, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins);
+void count_plan(int what, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins, int *route, int *launches, int64_t *info6);
+int histogram_range_check(const char *who, int64_t bins, double *lo, double *hi);  // numpy's refusals; a range of one point is widened by 0.5 each way
+int histogram_edges(int dtype, int64_t bins, double lo, double hi, void *edges_host);
+int launch_searchsorted(int side, int dtype, const void *edges, int64_t n_edges, const void *x, const int64_t *shape, const int64_t *strides, int ndim, int64_t *out,
+                        hipStream_t s);
+int launch_bincount(int mode, int dtype, const void *ids, const int64_t *shape, const int64_t *strides, int ndim, int64_t nbins, int64_t *counts, int64_t *bad_out,
+                    hipStream_t s);
+int launch_histogram(int flags, int dtype, const void *x, const int64_t *shape, const int64_t *strides, int ndim, const void *edges, int64_t bins, double lo, double hi,
+                     int64_t *counts, hipStream_t s);
+
 }  // namespace smhip
