@@ -58,6 +58,10 @@ concept ArithmeticOrComplex =
 template <ArithmeticOrComplex T>
 class SMArray;
 
+// A comparison that has not been evaluated yet: what `a > 0.0f` gives (defined below the class).
+template <typename T>
+struct Cond;
+
 // What take / take_along_axis do with an index outside [-R, R) of an axis of R elements (smhip.h: smhip_index_mode).
 enum class index_mode {
     checked = SMHIP_INDEX_CHECKED,  // numpy's rule: negatives count from the end, anything else out of range throws std::out_of_range
@@ -109,6 +113,7 @@ struct FusionStats {
     unsigned long long takes = 0;               // smhip_take_axis calls: take / take_along_axis / take_flat
     unsigned long long scatters = 0;            // smhip_scatter_axis calls: put_along_axis / put / put_flat / scatter_add / index_add
     unsigned long long counts = 0;              // smhip_searchsorted / smhip_bincount / smhip_histogram calls
+    unsigned long long selects = 0;             // smhip_where / smhip_select_count / smhip_select calls
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -119,6 +124,31 @@ inline void end_of_expression(int exceptions_at_birth) {
         return;
     }
     flush_pending();
+}
+
+// numpy's broadcasting of `other` into `shape`, aligned at the last axis; std::invalid_argument when the two do not broadcast.
+inline void broadcast_into(std::vector<std::size_t> &shape, const std::vector<std::size_t> &other, const char *who) {
+    if (other.size() > shape.size()) shape.insert(shape.begin(), other.size() - shape.size(), 1);
+    const std::size_t pad = shape.size() - other.size();
+    for (std::size_t d = 0; d < other.size(); ++d) {
+        std::size_t &n = shape[pad + d];
+        if (n == other[d] || other[d] == 1) continue;
+        if (n != 1) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + who + ": the shapes do not broadcast at axis " + std::to_string(pad + d));
+        n = other[d];
+    }
+}
+// The strides (in elements) of an operand seen over `over`, 0 along the axes it is broadcast; std::invalid_argument when it does not
+// broadcast TO `over`.
+inline std::vector<std::int64_t> strides_over(const std::vector<std::size_t> &shape, const std::vector<std::size_t> &strides, const std::vector<std::size_t> &over,
+                                              const char *who) {
+    if (shape.size() > over.size()) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + who + ": an operand has more axes than the result");
+    std::vector<std::int64_t> st(over.size(), 0);
+    const std::size_t pad = over.size() - shape.size();
+    for (std::size_t d = 0; d < shape.size(); ++d) {
+        if (shape[d] == over[pad + d]) st[pad + d] = shape[d] == 1 ? 0 : static_cast<std::int64_t>(strides[d]);
+        else if (shape[d] != 1) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + who + ": the shapes do not broadcast at axis " + std::to_string(pad + d));
+    }
+    return st;
 }
 
 // One allocation, shared by an owning array and every view of it.
@@ -994,6 +1024,53 @@ public:
         return count_between(edges, 0, 0.0, 0.0);
     }
 
+    // CHOOSING BY CONDITION (np.where, np.putmask, np.count_nonzero, np.flatnonzero, np.nonzero, a[mask]).  A condition is what the
+    // comparison operators below the class give -- `a > 0.0f`, `a <= b`, `0 == a` -- a sm::Cond<T>, evaluated inside the kernel that
+    // consumes it (the mask is never written to HBM); an SMArray<T> where a condition is expected stands for "nonzero".  Semantics are
+    // numpy's: a comparison with a NaN is false except !=, -0.0 == +0.0, a NaN is nonzero.  Operands may be views (copied dense
+    // first) or pending chains (evaluated first).
+    //   sm::where(c, a, b)        c ? a : b, a and b each an array or a T, everything broadcasting by numpy's rule; a dense array
+    //                             holding the chosen operand's own bits.  Asynchronous.
+    //   x.assign_where(c, v)      np.putmask / x[mask] = v, in place; c and v broadcast to x's shape.  A target that is not dense is
+    //                             staged like put.  Returns x.  Asynchronous.
+    //   sm::mask(c)               where(c, T{1}, T{0}): conditions then combine with the arithmetic operators.
+    //   sm::count_nonzero(c), sm::flatnonzero(c), sm::nonzero(c), x.select(c) / sm::select(x, c), sm::compress(c1d, x, axis)
+    //                             the size of the result depends on the data: each counts first and WAITS FOR THE STREAM ONCE to learn
+    //                             it, then allocates exactly and selects.  x.select(c) is x[mask] in row-major order; x may have another
+    //                             element type than the condition's operands, the shapes must be equal.
+    // std::invalid_argument: shapes that do not broadcast (where, assign_where) or are not equal (select).  Each library call is
+    // counted in sm::fusion_stats().selects.
+    SMArray &assign_where(const Cond<T> &c, const SMArray &v) { return assign_where_of(c, &v, T{}); }
+    SMArray &assign_where(const Cond<T> &c, T v) { return assign_where_of(c, nullptr, v); }
+    template <typename U>
+    SMArray select(const Cond<U> &c) const {
+        static_assert(hip::transport_of<T>::id >= 0 && (sizeof(T) == 4 || sizeof(T) == 8), "select: elements of 4 or 8 bytes");
+        if (c.shape() != _shape) throw std::invalid_argument("simpleMath/MI355X: select: the array and the condition have different shapes");
+        hip::DeviceGuard on(device());
+        const typename Cond<U>::Call call(c, _shape, "select");
+        const T *src = device_data();  // a pending chain that produces the array runs here
+        const std::int64_t total = call.count();
+        SMArray out = device_empty(std::vector<std::size_t>{static_cast<std::size_t>(total)});
+        if (total == 0) return out;
+        auto ss = hip::to_i64(_strides);
+        if (ss.empty()) ss = {1};
+        hip::check(smhip_select(SMHIP_SELECT_VALUES, call.cmp, hip::dtype_of<U>::id, call.x, call.sx.data(), call.y, call.sy.data(), &call.scalar, call.shape.data(),
+                                call.ndim(), src, ss.data(), static_cast<int>(sizeof(T)), out.device_data_mut(), total, nullptr));
+        ++detail::tls_fusion_stats.selects;
+        return out;
+    }
+    template <typename U>
+    SMArray select(const SMArray<U> &nonzero) const { return select(Cond<U>(nonzero)); }
+    // c ? a : b (a / b == nullptr: the scalar) over the broadcast shape: what sm::where calls.
+    static SMArray where_of(const Cond<T> &c, const SMArray *a, T sa, const SMArray *b, T sb) {
+        std::vector<std::size_t> shape = c.shape();
+        if (a) detail::broadcast_into(shape, a->_shape, "where");
+        if (b) detail::broadcast_into(shape, b->_shape, "where");
+        SMArray out = device_empty(std::vector<std::size_t>(shape));
+        if (out.totalSize != 0) run_where(c, a, sa, b, sb, shape, nullptr, out.device_data_mut());
+        return out;
+    }
+
 private:
     std::vector<std::size_t> _shape;
     std::vector<std::size_t> _strides;
@@ -1003,6 +1080,8 @@ private:
     SMArray() = default;  // internal: views and device-born results
 
     friend struct detail::Chain<T>;
+    template <typename U>
+    friend struct Cond;
 
     // Another handle on the same elements (same storage, offset, shape, strides): what a recorded chain keeps of an operand.
     SMArray alias() const {
@@ -1500,6 +1579,33 @@ private:
         return out;
     }
 
+    // ---- where: `target` (dense) is both b and the result when given (assign_where), else the result goes to `out`
+    static void run_where(const Cond<T> &c, const SMArray *a, T sa, const SMArray *b, T sb, const std::vector<std::size_t> &shape, SMArray *target, T *out) {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "where / assign_where: f32, f64, i32 and i64");
+        int device = c.right() ? common_device(c.left(), *c.right()) : c.left().device();
+        if (a) device = common_device(c.left(), *a);
+        if (b) device = common_device(c.left(), *b);
+        hip::DeviceGuard on(device);
+        if (target) out = target->data.storage()->dev_rw() + target->data.offset();  // before the operands' pointers: this may allocate
+        const typename Cond<T>::Call call(c, shape, "where");
+        std::vector<std::int64_t> sta, stb;
+        if (a) sta = detail::strides_over(a->_shape, a->_strides, shape, "where");
+        if (b) stb = detail::strides_over(b->_shape, b->_strides, shape, "where");
+        if (shape.empty()) sta = stb = {1};
+        const T *pa = a ? a->device_data() : nullptr, *pb = b ? b->device_data() : nullptr;  // pending chains run here
+        hip::check(smhip_where(call.cmp, hip::dtype_of<T>::id, call.x, call.sx.data(), call.y, call.sy.data(), &call.scalar, pa, sta.data(), &sa, pb, stb.data(), &sb,
+                               call.shape.data(), call.ndim(), out));
+        ++detail::tls_fusion_stats.selects;
+    }
+    SMArray &assign_where_of(const Cond<T> &c, const SMArray *v, T s) {
+        if (!is_dense()) return staged([&](SMArray &dense) { dense.assign_where_of(c, v, s); });
+        // the shapes are checked also when there is nothing to write
+        detail::strides_over(c.shape(), std::vector<std::size_t>(c.shape().size(), 0), _shape, "assign_where");
+        if (v) detail::strides_over(v->_shape, v->_strides, _shape, "assign_where");
+        if (totalSize != 0) run_where(c, v, s, this, T{}, _shape, this, nullptr);
+        return *this;
+    }
+
     // Device pointer to a dense version of this array (itself when already dense).
     const T *dense_device(std::unique_ptr<SMArray> &holder) const {
         if (is_dense()) return device_data();
@@ -1687,6 +1793,119 @@ private:
 };
 
 }  // namespace detail
+
+// A CONDITION: cmp(x, rhs) with rhs an array or a scalar, or "x is nonzero".  A small value: handles on its operands (which keep
+// their storage alive, so `auto c = a * b > 1.0f;` is safe) and the comparison.  Nothing is computed until sm::where, assign_where,
+// count_nonzero, flatnonzero, nonzero or select asks, and then inside their kernels.  It is not an array, and it does not convert to
+// bool: `if (a > b)` does not compile.
+template <typename T>
+struct Cond {
+    static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "a condition compares float, double, int or std::int64_t arrays");
+    Cond(const SMArray<T> &nonzero) : x_(nonzero.alias()) {}  // implicit: an array where a condition is expected stands for "nonzero"
+    Cond(const SMArray<T> &x, smhip_cmp cmp, const SMArray<T> &y) : x_(x.alias()), y_(new SMArray<T>(y.alias())), cmp_(cmp) {}
+    Cond(const SMArray<T> &x, smhip_cmp cmp, T scalar) : x_(x.alias()), cmp_(cmp), scalar_(scalar) {}
+
+    const SMArray<T> &left() const { return x_; }
+    const SMArray<T> *right() const { return y_.get(); }  // nullptr: the right-hand side is scalar() (or there is none: nonzero)
+    smhip_cmp cmp() const { return cmp_; }
+    T scalar() const { return scalar_; }
+    // x against y by numpy's rule; std::invalid_argument when they do not broadcast.
+    std::vector<std::size_t> shape() const {
+        std::vector<std::size_t> s = x_.shape();
+        if (y_) detail::broadcast_into(s, y_->shape(), "condition");
+        return s;
+    }
+
+    // The condition as the C ABI takes it, seen over `over`: device pointers (pending chains are evaluated here), strides in elements.
+    struct Call {
+        std::vector<std::int64_t> shape, sx, sy;
+        const T *x = nullptr, *y = nullptr;
+        T scalar;
+        int cmp;
+        Call(const Cond &c, const std::vector<std::size_t> &over, const char *who) : shape(hip::to_i64(over)), scalar(c.scalar_), cmp(c.cmp_) {
+            sx = detail::strides_over(c.x_.shape(), c.x_.strides(), over, who);
+            if (c.y_) sy = detail::strides_over(c.y_->shape(), c.y_->strides(), over, who);
+            if (shape.empty()) shape = {1}, sx = {1}, sy = std::vector<std::int64_t>(c.y_ ? 1 : 0, 1);  // a 0-d array is one element
+            for (std::int64_t n : shape) empty |= n == 0;
+            if (empty) return;
+            x = c.x_.device_data();
+            if (c.y_) y = c.y_->device_data();
+        }
+        int ndim() const { return static_cast<int>(shape.size()); }
+        // np.count_nonzero: one word from the pool, downloaded -- WAITS FOR THE STREAM.
+        std::int64_t count() const {
+            if (empty) return 0;
+            hip::DeviceBuffer word(sizeof(std::int64_t));
+            hip::check(smhip_select_count(cmp, hip::dtype_of<T>::id, x, sx.data(), y, sy.data(), &scalar, shape.data(), ndim(), word.template as<std::int64_t>()));
+            ++detail::tls_fusion_stats.selects;
+            std::int64_t n = 0;
+            hip::check(smhip_download(&n, word.get(), sizeof n));
+            return n;
+        }
+        bool empty = false;
+    };
+
+    std::int64_t count_nonzero() const {
+        const auto over = shape();
+        hip::DeviceGuard on(device());
+        return Call(*this, over, "count_nonzero").count();
+    }
+    // The row-major positions where the condition holds, shape {count}.
+    SMArray<std::int64_t> flatnonzero() const {
+        const auto over = shape();
+        hip::DeviceGuard on(device());
+        const Call call(*this, over, "flatnonzero");
+        const std::int64_t total = call.count();
+        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{static_cast<std::size_t>(total)});
+        if (total == 0) return out;
+        hip::check(smhip_select(SMHIP_SELECT_INDEX, call.cmp, hip::dtype_of<T>::id, call.x, call.sx.data(), call.y, call.sy.data(), &call.scalar, call.shape.data(),
+                                call.ndim(), nullptr, nullptr, 0, out.device_data_mut(), total, nullptr));
+        ++detail::tls_fusion_stats.selects;
+        return out;
+    }
+    // One array of shape {count} per axis: the coordinates where the condition holds, in row-major order.
+    std::vector<SMArray<std::int64_t>> nonzero() const {
+        const auto over = shape();
+        hip::DeviceGuard on(device());
+        const Call call(*this, over, "nonzero");
+        const std::int64_t total = call.count();
+        const std::size_t nd = static_cast<std::size_t>(call.ndim());
+        std::vector<SMArray<std::int64_t>> out;
+        if (total == 0) {
+            for (std::size_t d = 0; d < nd; ++d) out.push_back(SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{0}));
+            return out;
+        }
+        SMArray<std::int64_t> planes = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{nd, static_cast<std::size_t>(total)});
+        hip::check(smhip_select(SMHIP_SELECT_COORDS, call.cmp, hip::dtype_of<T>::id, call.x, call.sx.data(), call.y, call.sy.data(), &call.scalar, call.shape.data(),
+                                call.ndim(), nullptr, nullptr, 0, planes.device_data_mut(), total, nullptr));
+        ++detail::tls_fusion_stats.selects;
+        for (std::size_t d = 0; d < nd; ++d) out.push_back(planes(d, SLICE_ALL));  // views of the one buffer
+        return out;
+    }
+
+private:
+    int device() const { return y_ ? SMArray<T>::common_device(x_, *y_) : x_.device(); }
+    SMArray<T> x_;
+    std::unique_ptr<SMArray<T>> y_;
+    smhip_cmp cmp_ = SMHIP_CMP_NONZERO;
+    T scalar_{};
+};
+
+// == != < <= > >= between two arrays, an array and a scalar, or a scalar and an array (the comparison turned round): a Cond<T>.
+#define SM_COMPARISON(OP, CMP, TURNED)                                                                                       \
+    template <typename T>                                                                                                    \
+    Cond<T> operator OP(const SMArray<T> &x, const SMArray<T> &y) { return Cond<T>(x, CMP, y); }                             \
+    template <typename T>                                                                                                    \
+    Cond<T> operator OP(const SMArray<T> &x, std::type_identity_t<T> s) { return Cond<T>(x, CMP, s); }                       \
+    template <typename T>                                                                                                    \
+    Cond<T> operator OP(std::type_identity_t<T> s, const SMArray<T> &x) { return Cond<T>(x, TURNED, s); }
+SM_COMPARISON(==, SMHIP_CMP_EQ, SMHIP_CMP_EQ)
+SM_COMPARISON(!=, SMHIP_CMP_NE, SMHIP_CMP_NE)
+SM_COMPARISON(<, SMHIP_CMP_LT, SMHIP_CMP_GT)
+SM_COMPARISON(<=, SMHIP_CMP_LE, SMHIP_CMP_GE)
+SM_COMPARISON(>, SMHIP_CMP_GT, SMHIP_CMP_LT)
+SM_COMPARISON(>=, SMHIP_CMP_GE, SMHIP_CMP_LE)
+#undef SM_COMPARISON
 
 // What the operator fusion did on the calling thread so far (chains evaluated as one call, operators inside them, deferred
 // operators that stayed alone).

@@ -342,6 +342,64 @@ std::pair<SMArray<std::int64_t>, SMArray<T>> histogram(const SMArray<T> &x, std:
 template <typename T>
 SMArray<std::int64_t> histogram(const SMArray<T> &x, const SMArray<T> &edges) { return x.histogram(edges); }
 
+// Choosing by condition (np.where, np.count_nonzero, np.flatnonzero, np.nonzero, a[mask], np.compress).  A condition is a comparison of
+// arrays -- `a > 0.0f`, `a <= b`, `0 == a`: a sm::Cond<T>, evaluated inside the kernel that consumes it -- or an array, which stands for
+// "nonzero".  where(c, a, b): c ? a : b with a and b each an array or a scalar, all broadcasting; mask(c): where(c, 1, 0), so that
+// conditions combine with the arithmetic operators (and: m1 * m2; or: m1 + m2 - m1 * m2; not: -m + 1).  count_nonzero, flatnonzero,
+// nonzero, select and compress have results whose size depends on the data: each WAITS FOR THE STREAM ONCE, to learn it.  Semantics as
+// SMArray::assign_where / select (SMArray.h) and smhip_where / smhip_select_count / smhip_select.
+namespace detail {
+// An operand of where: an array or a scalar.
+template <typename T>
+struct WhereArg {
+    const SMArray<T> *array = nullptr;
+    T value{};
+    WhereArg(const SMArray<T> &a) : array(&a) {}
+    WhereArg(T v) : value(v) {}
+};
+}  // namespace detail
+template <typename T>
+SMArray<T> where(const Cond<T> &c, const std::type_identity_t<detail::WhereArg<T>> &a, const std::type_identity_t<detail::WhereArg<T>> &b) {
+    return SMArray<T>::where_of(c, a.array, a.value, b.array, b.value);
+}
+template <typename T>
+SMArray<T> where(const SMArray<T> &nonzero, const std::type_identity_t<detail::WhereArg<T>> &a, const std::type_identity_t<detail::WhereArg<T>> &b) {
+    return SMArray<T>::where_of(Cond<T>(nonzero), a.array, a.value, b.array, b.value);
+}
+template <typename T>
+SMArray<T> mask(const Cond<T> &c) { return SMArray<T>::where_of(c, nullptr, T{1}, nullptr, T{0}); }
+template <typename T>
+SMArray<T> mask(const SMArray<T> &nonzero) { return mask(Cond<T>(nonzero)); }
+template <typename T>
+std::int64_t count_nonzero(const Cond<T> &c) { return c.count_nonzero(); }
+template <typename T>
+std::int64_t count_nonzero(const SMArray<T> &arr) { return Cond<T>(arr).count_nonzero(); }
+template <typename T>
+SMArray<std::int64_t> flatnonzero(const Cond<T> &c) { return c.flatnonzero(); }
+template <typename T>
+SMArray<std::int64_t> flatnonzero(const SMArray<T> &arr) { return Cond<T>(arr).flatnonzero(); }
+template <typename T>
+std::vector<SMArray<std::int64_t>> nonzero(const Cond<T> &c) { return c.nonzero(); }
+template <typename T>
+std::vector<SMArray<std::int64_t>> nonzero(const SMArray<T> &arr) { return Cond<T>(arr).nonzero(); }
+template <typename T, typename U>
+SMArray<T> select(const SMArray<T> &arr, const Cond<U> &c) { return arr.select(c); }
+template <typename T, typename U>
+SMArray<T> select(const SMArray<T> &arr, const SMArray<U> &nonzero) { return arr.select(nonzero); }
+// np.compress(cond1d, arr, axis): the slices of arr along `axis` where the 1-D condition holds, take(arr, flatnonzero(cond1d), axis).
+// std::invalid_argument when the condition is not 1-D or its length differs from the axis.
+template <typename U, typename T>
+SMArray<T> compress(const Cond<U> &c, const SMArray<T> &arr, int axis) {
+    const int nd = static_cast<int>(arr.shape().size()), ax = axis < 0 ? axis + nd : axis;
+    if (ax < 0 || ax >= nd) throw std::invalid_argument("simpleMath/MI355X: compress: axis " + std::to_string(axis) + " of an array of rank " + std::to_string(nd));
+    const auto cs = c.shape();
+    if (cs.size() != 1 || cs[0] != arr.shape()[ax])
+        throw std::invalid_argument("simpleMath/MI355X: compress: the condition must be 1-D and as long as the axis (" + std::to_string(arr.shape()[ax]) + ")");
+    return arr.take(c.flatnonzero(), ax, index_mode::clip);  // the positions are valid by construction
+}
+template <typename U, typename T>
+SMArray<T> compress(const SMArray<U> &nonzero, const SMArray<T> &arr, int axis) { return compress(Cond<U>(nonzero), arr, axis); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

@@ -596,6 +596,68 @@ int smhip_histogram_edges(int dtype, int64_t bins, double lo, double hi, void *e
 int smhip_count_plan(int what, int flags, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins,
                      int *route, int *launches, int64_t *info6);
 
+/* ------------------------------------------ selection by condition: where / count_nonzero / nonzero / a[mask] */
+/* Choosing elements by a condition.  A CONDITION is cmp(x, rhs), evaluated inside the kernels that consume it: the mask is never
+ * written to memory.  The contract:
+ *   condition    `x` is a view over `shape` (strides in ELEMENTS, >= 0, rank 1 .. SMHIP_MAX_NDIM) of one of the four element types.
+ *                `rhs` is an array `y` of the same type whose strides broadcast against `shape` (0 along a broadcast axis), or, with
+ *                y == NULL, ONE scalar of that type in HOST memory (read before the call returns).  SMHIP_CMP_NONZERO ignores rhs.
+ *   semantics    numpy's, which are IEEE's: a comparison with a NaN is false, except NE, which is true; -0.0 == +0.0; NONZERO is
+ *                x != 0, so a NaN is nonzero and -0.0 is not; integer comparisons are exact.
+ *   where        out = cond ? a : b over `shape`, out dense row-major.  a and b are each an array of x's type with strides that
+ *                broadcast against `shape`, or (NULL) one scalar in host memory.  The result holds the chosen operand's own BITS
+ *                (which zero, which NaN payload).  out may BE any one of x, y, a, b when that operand is dense row-major over `shape`
+ *                (np.putmask, a[mask] = v); any other overlap of out with an operand is refused.  Operands that are dense (or
+ *                scalars) go through one pass of 16-byte loads and stores, operands given by the same pointer loaded once; an
+ *                operand that is not dense row-major (transposed, stepped, broadcast) is copied dense first (SMHIP_SELECT_COPY).
+ *   count        *count_dev = the number of elements where the condition holds (np.count_nonzero).
+ *   select       the compaction: writes the first min(total, capacity) selected items, in ROW-MAJOR order of `shape`, to `out`, and
+ *                the total to *count_dev (which may be NULL).  `what`:
+ *                  SMHIP_SELECT_INDEX   the row-major linear index, int64_t (np.flatnonzero);
+ *                  SMHIP_SELECT_COORDS  ndim planes of `capacity` int64_t each: out[d * capacity + k] = coordinate d of the k-th
+ *                                       selected element (np.nonzero);
+ *                  SMHIP_SELECT_VALUES  src[...] at the selected positions, src a view over `shape` of 4- or 8-byte elements
+ *                                       (src_elem_bytes) whose type need not be x's: the bits are copied (a[mask], np.extract).
+ *                Nothing at or past item `capacity` of out is written, and no address outside an operand is formed.
+ *   kernels      tiles of 256 lanes x 8 16-byte vectors.  Three launches, no workgroup waiting on another: (1) one count per tile,
+ *                (2) the exclusive prefix of the counts in int64_t (and the total), (3) the condition evaluated again, every lane
+ *                writing at its rank.  x is read twice.  Up to a threshold one workgroup does all of it in ONE launch.  x, y or src
+ *                that is not dense row-major is copied dense first, one launch each.
+ *   determinism  the order is fixed by the shape, every count is an integer: the same bytes on every run, stream and grid.
+ * Checked before any device is touched (SMHIP_ERR_INVALID): cmp, what, dtype, ndim, src_elem_bytes, null shape / strides, negative
+ * extents or strides, a negative capacity, spans past 2^59 elements, null pointers where there is something to read or write,
+ * pointers that are not aligned to their element, out or count_dev overlapping an operand or each other (for smhip_where: any
+ * overlap but the in-place one above).  No elements: where and select write nothing, the counts are 0.  Asynchronous,
+ * stream-ordered; recorded tiny operators are flushed first. */
+typedef enum smhip_cmp {
+    SMHIP_CMP_NONZERO = 0, SMHIP_CMP_EQ = 1, SMHIP_CMP_NE = 2, SMHIP_CMP_LT = 3, SMHIP_CMP_LE = 4, SMHIP_CMP_GT = 5, SMHIP_CMP_GE = 6
+} smhip_cmp;
+typedef enum smhip_select_what {
+    SMHIP_SELECT_INDEX = 0, SMHIP_SELECT_COORDS = 1, SMHIP_SELECT_VALUES = 2,
+    SMHIP_SELECT_COUNT = 3, SMHIP_SELECT_WHERE = 4 /* these two name smhip_select_count and smhip_where to smhip_select_plan only */
+} smhip_select_what;
+int smhip_where(int cmp, int dtype, const void *x, const int64_t *x_strides, const void *y, const int64_t *y_strides,
+                const void *rhs_scalar_host, const void *a, const int64_t *a_strides, const void *a_scalar_host,
+                const void *b, const int64_t *b_strides, const void *b_scalar_host, const int64_t *shape, int ndim, void *out);
+int smhip_select_count(int cmp, int dtype, const void *x, const int64_t *x_strides, const void *y, const int64_t *y_strides,
+                       const void *rhs_scalar_host, const int64_t *shape, int ndim, int64_t *count_dev);
+/* src, src_strides and src_elem_bytes are read for SMHIP_SELECT_VALUES only.  out: capacity items (COORDS: ndim * capacity). */
+int smhip_select(int what, int cmp, int dtype, const void *x, const int64_t *x_strides, const void *y, const int64_t *y_strides,
+                 const void *rhs_scalar_host, const int64_t *shape, int ndim, const void *src, const int64_t *src_strides,
+                 int src_elem_bytes, void *out, int64_t capacity, int64_t *count_dev_or_null);
+/* Host only, no device touched: the route a call would take (for smhip_select, one with capacity > 0).  y_strides NULL: a scalar rhs.
+ * a_strides: src's strides for VALUES, a's for WHERE (NULL: a scalar there, unused elsewhere); b_strides: b's for WHERE.
+ * *route = SMHIP_SELECT_ROUTE_* ORed with the flag below; *launches = the kernel launches of the call; info4 = {tiles, the elements
+ * of a tile for this element type, the largest element count that takes the one-workgroup route, operands copied dense first}.
+ * Any output may be NULL.  The planner's test hook. */
+#define SMHIP_SELECT_ROUTE_NONE 0  /* no elements: nothing to launch */
+#define SMHIP_SELECT_ROUTE_ONE 1   /* count / select: one workgroup walks the tiles with a carry, one launch */
+#define SMHIP_SELECT_ROUTE_TILES 2 /* count: a count per tile, then their fold; select: counts, their prefix, the writes */
+#define SMHIP_SELECT_ROUTE_DENSE 3 /* where: one pass over dense operands (large ones in pieces, one launch each) */
+#define SMHIP_SELECT_COPY 0x100    /* an operand is not dense row-major and is copied dense first (one launch each) */
+int smhip_select_plan(int what, int cmp, int dtype, const int64_t *shape, int ndim, const int64_t *x_strides, const int64_t *y_strides,
+                      const int64_t *a_strides, const int64_t *b_strides, int *route, int *launches, int64_t *info4);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

@@ -70,6 +70,14 @@ HISTOGRAM_UNIFORM = 1  # smhip_histogram's flag: the table is the uniform one of
 # smhip_count_plan's route word: a route in the low byte, the flag above it
 COUNT_ROUTE_NONE, COUNT_ROUTE_LDS, COUNT_ROUTE_GLOBAL = range(3)
 COUNT_COPY = 0x100
+CMP_NONZERO, CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(7)  # smhip_cmp
+CMPS = {"nonzero": CMP_NONZERO, "eq": CMP_EQ, "ne": CMP_NE, "lt": CMP_LT, "le": CMP_LE, "gt": CMP_GT, "ge": CMP_GE,
+        "==": CMP_EQ, "!=": CMP_NE, "<": CMP_LT, "<=": CMP_LE, ">": CMP_GT, ">=": CMP_GE}
+SELECT_INDEX, SELECT_COORDS, SELECT_VALUES, SELECT_COUNT, SELECT_WHERE = range(5)  # smhip_select_what (the last two: smhip_select_plan only)
+SELECT_OPS = {"index": SELECT_INDEX, "coords": SELECT_COORDS, "values": SELECT_VALUES, "count": SELECT_COUNT, "where": SELECT_WHERE}
+# smhip_select_plan's route word: a route in the low byte, the flag above it
+SELECT_ROUTE_NONE, SELECT_ROUTE_ONE, SELECT_ROUTE_TILES, SELECT_ROUTE_DENSE = range(4)
+SELECT_COPY = 0x100
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -1076,6 +1084,158 @@ class Smhip:
         route, launches, info = C.c_int(0), C.c_int(0), (C.c_int64 * 6)()
         self._ck(self.c.smhip_count_plan(C.c_int(what), C.c_int(HISTOGRAM_UNIFORM if uniform else 0), C.c_int(dtype), arr(shape), arr(strides), C.c_int(ndim),
                                          C.c_int64(int(bins)), C.byref(route), C.byref(launches), info))
+        return route.value, launches.value, tuple(int(v) for v in info)
+
+    # -- choosing by condition --------------------------------------------------------
+    def _cond(self, cond, who):
+        """A condition -> (cmp, x, y or None, the scalar as a 1-element array of x's dtype or None).  `cond` is a DeviceArray
+        (nonzero) or a tuple (x, "gt", rhs) with rhs a DeviceArray of x's dtype and shape or a Python / numpy scalar."""
+        if isinstance(cond, DeviceArray):
+            cond = (cond, "nonzero", None)
+        if not (isinstance(cond, tuple) and len(cond) == 3 and isinstance(cond[0], DeviceArray)):
+            raise ValueError(f"{who}: a condition is a DeviceArray or a tuple (x, cmp, rhs)")
+        x, cmp, rhs = cond
+        if x.dtype not in DTYPES:
+            raise ValueError(f"{who}: dtype {x.dtype} (f32, f64, i32 and i64 only)")
+        if cmp not in CMPS:
+            raise ValueError(f"{who}: comparison {cmp!r} (one of {sorted(CMPS)})")
+        if CMPS[cmp] == CMP_NONZERO:
+            return CMP_NONZERO, x, None, None
+        if isinstance(rhs, DeviceArray):
+            if rhs.dtype != x.dtype:
+                raise ValueError(f"{who}: the condition compares {x.dtype} with {rhs.dtype}")
+            return CMPS[cmp], x, self._broadcast_to(rhs, x.shape, who), None
+        if rhs is None:
+            raise ValueError(f"{who}: comparison {cmp!r} needs a right-hand side")
+        return CMPS[cmp], x, None, np.array([rhs]).astype(x.dtype)
+
+    def _broadcast_to(self, d, shape, who):
+        """`d` as a view over `shape` (numpy's rule: sizes of 1 and missing leading axes get stride 0)."""
+        shape = tuple(shape)
+        if d.shape == shape:
+            return d
+        if d.ndim > len(shape):
+            raise ValueError(f"{who}: shape {d.shape} does not broadcast to {shape}")
+        pad = len(shape) - d.ndim
+        strides = [0] * pad
+        for n, st, want in zip(d.shape, d.strides, shape[pad:]):
+            if n != want and n != 1:
+                raise ValueError(f"{who}: shape {d.shape} does not broadcast to {shape}")
+            strides.append(st if n == want and n != 1 else 0)
+        return DeviceArray(self, d.base_ptr, d.dtype, shape, strides, d.offset, d._owner)
+
+    @staticmethod
+    def _cond_args(cmp, x, y, s):
+        return (C.c_int(cmp), C.c_int(DTYPES[x.dtype]), C.c_void_p(x.ptr), _i64(x.strides), C.c_void_p(y.ptr if y is not None else 0),
+                _i64(y.strides) if y is not None else None, s.ctypes.data_as(C.c_void_p) if s is not None else None)
+
+    def where(self, cond, a, b, out: DeviceArray | None = None):
+        """np.where(cond, a, b) -> a dense DeviceArray of the condition's shape and dtype (or into `out`, which may be one of the
+        operands when that one is dense: np.putmask).  `a` and `b` are each a DeviceArray of that dtype that broadcasts to the
+        condition's shape, or a scalar.  The result holds the chosen operand's own bits.  Asynchronous."""
+        cmp, x, y, s = self._cond(cond, "where")
+        ops, keep = [], []
+        for name, v in (("a", a), ("b", b)):
+            if isinstance(v, DeviceArray):
+                if v.dtype != x.dtype:
+                    raise ValueError(f"where: {name} is {v.dtype}, the condition {x.dtype}")
+                v = self._broadcast_to(v, x.shape, "where")
+                ops += [C.c_void_p(v.ptr), _i64(v.strides), None]
+            else:
+                v = np.array([v]).astype(x.dtype)
+                ops += [C.c_void_p(0), None, v.ctypes.data_as(C.c_void_p)]
+            keep.append(v)   # alive until the call returns
+        if out is None:
+            out = self.empty(x.shape, x.dtype)
+        elif out.dtype != x.dtype or out.shape != x.shape or not out.is_dense():
+            raise ValueError(f"where: out must be a dense {x.dtype} array of shape {x.shape}")
+        self._ck(self.c.smhip_where(*self._cond_args(cmp, x, y, s), *ops, _i64(x.shape), C.c_int(x.ndim), C.c_void_p(out.ptr)))
+        del keep
+        return out
+
+    def count_nonzero(self, cond):
+        """np.count_nonzero(cond) -> int.  THIS WAITS FOR THE STREAM: the count is read back from the device."""
+        cmp, x, y, s = self._cond(cond, "count_nonzero")
+        word = self.empty((1,), np.int64)
+        self._ck(self.c.smhip_select_count(*self._cond_args(cmp, x, y, s), _i64(x.shape), C.c_int(x.ndim), C.c_void_p(word.ptr)))
+        return self.read_i64(word.ptr)
+
+    def _compact(self, what, cond, src, who):
+        cmp, x, y, s = self._cond(cond, who)
+        if src is not None:
+            if src.shape != x.shape:
+                raise ValueError(f"{who}: the array has shape {src.shape}, the condition {x.shape}")
+            if src.dtype.itemsize not in (4, 8):
+                raise ValueError(f"{who}: elements of {src.dtype.itemsize} bytes (4 or 8)")
+        word = self.empty((1,), np.int64)
+        args = self._cond_args(cmp, x, y, s)
+        self._ck(self.c.smhip_select_count(*args, _i64(x.shape), C.c_int(x.ndim), C.c_void_p(word.ptr)))
+        total = self.read_i64(word.ptr)   # waits for the stream
+        planes = x.ndim if what == SELECT_COORDS else 1
+        out = self.empty((planes * total,), src.dtype if src is not None else np.int64)
+        self._ck(self.c.smhip_select(C.c_int(what), *args, _i64(x.shape), C.c_int(x.ndim), C.c_void_p(src.ptr if src is not None else 0),
+                                     _i64(src.strides) if src is not None else None, C.c_int(src.dtype.itemsize if src is not None else 0),
+                                     C.c_void_p(out.ptr), C.c_int64(total), None))
+        return out, total
+
+    def flatnonzero(self, cond):
+        """np.flatnonzero(cond) -> an int64 DeviceArray of shape (count,): the row-major positions where the condition holds.
+        THIS WAITS FOR THE STREAM ONCE, to learn the size: count, read it back, allocate exactly, select."""
+        return self._compact(SELECT_INDEX, cond, None, "flatnonzero")[0]
+
+    def nonzero(self, cond):
+        """np.nonzero(cond) -> a tuple of ndim int64 DeviceArrays of shape (count,), one per axis.  THIS WAITS FOR THE STREAM ONCE,
+        to learn the size."""
+        out, total = self._compact(SELECT_COORDS, cond, None, "nonzero")
+        ndim = cond.ndim if isinstance(cond, DeviceArray) else cond[0].ndim
+        return tuple(DeviceArray(self, out.base_ptr, np.int64, (total,), (1,), d * total, out._owner) for d in range(ndim))
+
+    def select(self, a: DeviceArray, cond):
+        """a[mask] -> a DeviceArray of a's dtype and shape (count,): the elements of `a` where the condition holds, row-major.  `a`
+        has the condition's shape and any 4- or 8-byte dtype.  THIS WAITS FOR THE STREAM ONCE, to learn the size."""
+        return self._compact(SELECT_VALUES, cond, a, "select")[0]
+
+    def where_raw(self, cmp, dtype, x_ptr, x_strides, y_ptr, y_strides, rhs, a_ptr, a_strides, a_scalar, b_ptr, b_strides, b_scalar, shape, out_ptr, ndim=None):
+        """smhip_where with every argument as given (argument-validation tests); the scalars are numpy arrays of one element or
+        None; ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        host = lambda v: v.ctypes.data_as(C.c_void_p) if v is not None else None  # noqa: E731
+        return self.c.smhip_where(C.c_int(cmp), C.c_int(dtype), C.c_void_p(x_ptr), arr(x_strides), C.c_void_p(y_ptr), arr(y_strides), host(rhs),
+                                  C.c_void_p(a_ptr), arr(a_strides), host(a_scalar), C.c_void_p(b_ptr), arr(b_strides), host(b_scalar), arr(shape),
+                                  C.c_int(ndim), C.c_void_p(out_ptr))
+
+    def select_count_raw(self, cmp, dtype, x_ptr, x_strides, y_ptr, y_strides, rhs, shape, count_ptr, ndim=None):
+        """smhip_select_count with every argument as given; `rhs` a numpy array of one element or None."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        return self.c.smhip_select_count(C.c_int(cmp), C.c_int(dtype), C.c_void_p(x_ptr), arr(x_strides), C.c_void_p(y_ptr), arr(y_strides),
+                                         rhs.ctypes.data_as(C.c_void_p) if rhs is not None else None, arr(shape), C.c_int(ndim), C.c_void_p(count_ptr))
+
+    def select_raw(self, what, cmp, dtype, x_ptr, x_strides, y_ptr, y_strides, rhs, shape, src_ptr, src_strides, src_elem_bytes, out_ptr, capacity, count_ptr=0,
+                   ndim=None):
+        """smhip_select with every argument as given; `rhs` a numpy array of one element or None."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        return self.c.smhip_select(C.c_int(what), C.c_int(cmp), C.c_int(dtype), C.c_void_p(x_ptr), arr(x_strides), C.c_void_p(y_ptr), arr(y_strides),
+                                   rhs.ctypes.data_as(C.c_void_p) if rhs is not None else None, arr(shape), C.c_int(ndim), C.c_void_p(src_ptr), arr(src_strides),
+                                   C.c_int(src_elem_bytes), C.c_void_p(out_ptr), C.c_int64(capacity), C.c_void_p(count_ptr))
+
+    def select_plan(self, what, dtype, shape, x_strides, y_strides=None, a_strides=None, b_strides=None, cmp=CMP_GT, ndim=None):
+        """smhip_select_plan (host only): (route word, launches, (tiles, elements per tile, the largest element count of the
+        one-workgroup route, operands copied)) for `what` ("index", "coords", "values", "count", "where") over a condition of this
+        shape; strides in elements, None for a scalar or an operand the call does not have."""
+        what = SELECT_OPS[what] if not isinstance(what, int) else what
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        route, launches, info = C.c_int(0), C.c_int(0), (C.c_int64 * 4)()
+        self._ck(self.c.smhip_select_plan(C.c_int(what), C.c_int(cmp), C.c_int(dtype), arr(shape), C.c_int(ndim), arr(x_strides), arr(y_strides), arr(a_strides),
+                                          arr(b_strides), C.byref(route), C.byref(launches), info))
         return route.value, launches.value, tuple(int(v) for v in info)
 
     def sum(self, a: DeviceArray):
