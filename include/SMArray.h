@@ -62,6 +62,10 @@ class SMArray;
 template <typename T>
 struct Cond;
 
+// What sm::unique_all returns: {values, index, inverse, counts} (defined below the class).
+template <typename T>
+struct UniqueAll;
+
 // What take / take_along_axis do with an index outside [-R, R) of an axis of R elements (smhip.h: smhip_index_mode).
 enum class index_mode {
     checked = SMHIP_INDEX_CHECKED,  // numpy's rule: negatives count from the end, anything else out of range throws std::out_of_range
@@ -114,6 +118,7 @@ struct FusionStats {
     unsigned long long scatters = 0;            // smhip_scatter_axis calls: put_along_axis / put / put_flat / scatter_add / index_add
     unsigned long long counts = 0;              // smhip_searchsorted / smhip_bincount / smhip_histogram calls
     unsigned long long selects = 0;             // smhip_where / smhip_select_count / smhip_select calls
+    unsigned long long uniques = 0;             // smhip_runs_count / smhip_runs calls: unique_* / unique_consecutive / run_lengths (a count, then the runs)
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -1040,6 +1045,33 @@ public:
     //                             element type than the condition's operands, the shapes must be equal.
     // std::invalid_argument: shapes that do not broadcast (where, assign_where) or are not equal (select).  Each library call is
     // counted in sm::fusion_stats().selects.
+    // THE DISTINCT VALUES (np.unique on the row-major flattening, under the Array API's names).  values: ascending, -0 == +0, one NaN
+    // last (every NaN with equal_nan = false), each holding the bits of its FIRST occurrence; index: where that is in the flattening;
+    // inverse: shape {size}, the value number of every element, so values.take_flat(inverse) rebuilds the flattening (up to which zero
+    // and which NaN payload); counts: how often each value occurs.  The operand may be a view (copied dense) or a pending chain
+    // (evaluated first).  Each is ONE smhip_sort_axis call (positions only when index or inverse is wanted), a count of the runs, ONE
+    // WAIT FOR THE STREAM to learn how many there are, and one smhip_runs call into arrays of exactly that size; the two run calls are
+    // counted in sm::fusion_stats().uniques.  An empty operand gives arrays of shape {0}; 2^31 elements or more throw what sort_flat
+    // throws.  unique_consecutive / run_lengths do the same WITHOUT the sort and without that limit: the first element of every run of
+    // adjacent equal elements, and the runs' lengths (run-length encoding).  With inverse and index_add they make a group-by:
+    //   auto [keys, inverse] = sm::unique_inverse(k);  auto sums = sm::zeros<float>(keys.totalSize);  sums.index_add(inverse, v, 0);
+    SMArray unique_values(bool equal_nan = true) const { return runs_of(true, equal_nan, false, false, false).values; }
+    SMArray unique(bool equal_nan = true) const { return unique_values(equal_nan); }
+    std::pair<SMArray, SMArray<std::int64_t>> unique_counts(bool equal_nan = true) const {
+        UniqueAll<T> r = runs_of(true, equal_nan, false, false, true);
+        return {std::move(r.values), std::move(r.counts)};
+    }
+    std::pair<SMArray, SMArray<std::int64_t>> unique_inverse(bool equal_nan = true) const {
+        UniqueAll<T> r = runs_of(true, equal_nan, false, true, false);
+        return {std::move(r.values), std::move(r.inverse)};
+    }
+    UniqueAll<T> unique_all(bool equal_nan = true) const { return runs_of(true, equal_nan, true, true, true); }
+    SMArray unique_consecutive(bool equal_nan = true) const { return runs_of(false, equal_nan, false, false, false).values; }
+    std::pair<SMArray, SMArray<std::int64_t>> run_lengths(bool equal_nan = true) const {
+        UniqueAll<T> r = runs_of(false, equal_nan, false, false, true);
+        return {std::move(r.values), std::move(r.counts)};
+    }
+
     SMArray &assign_where(const Cond<T> &c, const SMArray &v) { return assign_where_of(c, &v, T{}); }
     SMArray &assign_where(const Cond<T> &c, T v) { return assign_where_of(c, nullptr, v); }
     template <typename U>
@@ -1606,6 +1638,45 @@ private:
         return *this;
     }
 
+    // The runs of the flattening (sort_first: of its stable ascending sort): count, wait, allocate exactly, emit.  A result that is not
+    // wanted comes back with shape {0}.
+    UniqueAll<T> runs_of(bool sort_first, bool equal_nan, bool want_index, bool want_inverse, bool want_counts) const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "unique / unique_consecutive: f32, f64, i32 and i64");
+        using Index = SMArray<std::int64_t>;
+        const auto none = [] { return std::vector<std::size_t>{0}; };
+        if (totalSize == 0) return UniqueAll<T>{device_empty(none()), Index::device_empty(none()), Index::device_empty(none()), Index::device_empty(none())};
+        hip::DeviceGuard on(device());
+        std::unique_ptr<SMArray> holder;
+        const T *in = dense_device(holder);  // a pending chain that produces this operand runs here
+        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
+        const int flags = equal_nan ? 0 : SMHIP_RUNS_NAN_DISTINCT;
+        const bool positions = sort_first && (want_index || want_inverse);
+        SMArray sorted = device_empty(std::vector<std::size_t>{sort_first ? totalSize : 0});
+        Index order = Index::device_empty(std::vector<std::size_t>{positions ? totalSize : 0});
+        const std::int64_t *ord = nullptr;
+        if (sort_first) {
+            hip::check(smhip_sort_axis(SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, &n, &one, 1, 0, sorted.device_data_mut(),
+                                       positions ? order.device_data_mut() : nullptr));
+            ++detail::tls_fusion_stats.sorts;
+            in = sorted.device_data();
+            if (positions) ord = order.device_data();
+        }
+        std::int64_t total = 0;
+        {
+            hip::DeviceBuffer word(sizeof(std::int64_t));
+            hip::check(smhip_runs_count(flags, hip::dtype_of<T>::id, in, n, word.template as<std::int64_t>()));
+            ++detail::tls_fusion_stats.uniques;
+            hip::check(smhip_download(&total, word.get(), sizeof total));  // waits for the stream
+        }
+        const std::size_t runs = static_cast<std::size_t>(total);
+        UniqueAll<T> r{device_empty(std::vector<std::size_t>{runs}), Index::device_empty(std::vector<std::size_t>{want_index ? runs : 0}),
+                       Index::device_empty(std::vector<std::size_t>{want_inverse ? totalSize : 0}), Index::device_empty(std::vector<std::size_t>{want_counts ? runs : 0})};
+        hip::check(smhip_runs(flags, hip::dtype_of<T>::id, in, n, ord, r.values.device_data_mut(), want_index ? r.index.device_data_mut() : nullptr,
+                              want_counts ? r.counts.device_data_mut() : nullptr, want_inverse ? r.inverse.device_data_mut() : nullptr, total, nullptr));
+        ++detail::tls_fusion_stats.uniques;
+        return r;
+    }
+
     // Device pointer to a dense version of this array (itself when already dense).
     const T *dense_device(std::unique_ptr<SMArray> &holder) const {
         if (is_dense()) return device_data();
@@ -1793,6 +1864,14 @@ private:
 };
 
 }  // namespace detail
+
+// What sm::unique_all returns (the Array API's names): the distinct values, where each first occurs in the flattening, the value
+// number of every element, and how often each value occurs.
+template <typename T>
+struct UniqueAll {
+    SMArray<T> values;
+    SMArray<std::int64_t> index, inverse, counts;
+};
 
 // A CONDITION: cmp(x, rhs) with rhs an array or a scalar, or "x is nonzero".  A small value: handles on its operands (which keep
 // their storage alive, so `auto c = a * b > 1.0f;` is safe) and the comparison.  Nothing is computed until sm::where, assign_where,

@@ -400,6 +400,25 @@ SMArray<T> compress(const Cond<U> &c, const SMArray<T> &arr, int axis) {
 template <typename U, typename T>
 SMArray<T> compress(const SMArray<U> &nonzero, const SMArray<T> &arr, int axis) { return compress(Cond<U>(nonzero), arr, axis); }
 
+// The distinct values (np.unique on the row-major flattening, the Array API's names): values ascending with one NaN last (every NaN
+// with equal_nan = false), the first occurrence of each, the value number of every element (shape {size}), how often each occurs.
+// unique_consecutive / run_lengths: the same without the sort -- the first element of every run of adjacent equal elements and the
+// runs' lengths.  Each waits for the stream once to learn the size.  Semantics as the members of the same names (SMArray.h) and smhip_runs.
+template <typename T>
+SMArray<T> unique_values(const SMArray<T> &arr, bool equal_nan = true) { return arr.unique_values(equal_nan); }
+template <typename T>
+SMArray<T> unique(const SMArray<T> &arr, bool equal_nan = true) { return arr.unique_values(equal_nan); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> unique_counts(const SMArray<T> &arr, bool equal_nan = true) { return arr.unique_counts(equal_nan); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> unique_inverse(const SMArray<T> &arr, bool equal_nan = true) { return arr.unique_inverse(equal_nan); }
+template <typename T>
+UniqueAll<T> unique_all(const SMArray<T> &arr, bool equal_nan = true) { return arr.unique_all(equal_nan); }
+template <typename T>
+SMArray<T> unique_consecutive(const SMArray<T> &arr, bool equal_nan = true) { return arr.unique_consecutive(equal_nan); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> run_lengths(const SMArray<T> &arr, bool equal_nan = true) { return arr.run_lengths(equal_nan); }
+
 // Block until every queued kernel has finished (operators are asynchronous;
 // anything that reads values on the host synchronises by itself).
 inline void synchronize() { hip::check(smhip_synchronize()); }

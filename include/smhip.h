@@ -658,6 +658,59 @@ int smhip_select(int what, int cmp, int dtype, const void *x, const int64_t *x_s
 int smhip_select_plan(int what, int cmp, int dtype, const int64_t *shape, int ndim, const int64_t *x_strides, const int64_t *y_strides,
                       const int64_t *a_strides, const int64_t *b_strides, int *route, int *launches, int64_t *info4);
 
+/* ------------------------------------------ the distinct values: unique / unique_consecutive (runs) */
+/* The RUNS of a dense 1-D array `s` of n elements.  On sorted input (smhip_sort_axis, ascending) the runs are the distinct values and
+ * the four results are np.unique's; on any input they are its run-length encoding (unique_consecutive).  The contract:
+ *   a run        a maximal stretch of adjacent elements that are THE SAME in smhip_sort_axis's order: equal numbers are the same, and
+ *                -0.0 == +0.0; two NaNs are the same whatever their sign or payload; integers compare exactly over their full width.
+ *                With SMHIP_RUNS_NAN_DISTINCT in `flags` a NaN is never the same as anything (numpy's equal_nan=False).  Whether `s`
+ *                is sorted is not checked.  There are U runs; run k starts at element start_k, start_0 = 0, and start_U stands for n.
+ *   count        *count_dev = U.
+ *   runs         for k < min(U, capacity), any subset of the four results (a NULL one is not produced):
+ *                  values_out[k]  = s[start_k], the BITS of that element (which zero, which NaN payload);
+ *                  index_out[k]   = order ? order[start_k] : start_k -- with `order` the positions a stable sort returned, the FIRST
+ *                                   occurrence of the value in the unsorted array (np.unique's return_index);
+ *                  counts_out[k]  = start_{k+1} - start_k, the length of the run (return_counts);
+ *                and for ALL n elements, whatever the capacity,
+ *                  inverse_out[order ? order[i] : i] = the number of the run element i lies in (return_inverse): with a sort's
+ *                                   positions, values_out[inverse_out[j]] is the unsorted array's element j.
+ *                *count_dev_or_null = U.  Nothing at or past item `capacity` of values, index and counts is written.  `order` is
+ *                n int64_t; an order[i] outside [0, n) writes nothing, so no address outside a buffer is ever formed.  If order is
+ *                not a permutation, the elements of inverse_out it does not name keep their bytes, and one it names twice holds
+ *                either run.
+ *   kernels      select's compaction with the flag of element i taken from TWO elements: i == 0 || !same(s[i - 1], s[i]).  Tiles of
+ *                256 lanes x 8 16-byte vectors (element-aligned: an operand off the 16-byte grid takes the same kernel); the left
+ *                neighbour of a vector's first element is one extra element load.  Launches, no workgroup waiting on another and no
+ *                atomics: (1) the flags counted per tile, (2) the exclusive prefix of the counts in int64_t and the total (select's
+ *                prefix kernel), (3) the flags again, every element ranked, and values, index and inverse written from that rank,
+ *                (4) ONLY WHEN counts_out IS GIVEN: pass 3 also writes each run's start to a pooled buffer of min(capacity + 1, n)
+ *                words, and one small launch over the runs takes adjacent differences, the last run ending at n -- a run's length
+ *                needs the next run's start, which another workgroup may hold, and a launch boundary orders the two without a
+ *                wait.  s is read twice.  Up to a threshold one workgroup does all of it in ONE launch.
+ *   determinism  the order is fixed by the data, every count is an integer: the same bytes on every run, stream and grid.
+ * Checked before any device is touched (SMHIP_ERR_INVALID): unknown flag bits, dtype (f32, f64, i32, i64), a negative n or capacity,
+ * n >= 2^59, a null s with n > 0, a null count_dev (smhip_runs_count), all four results null (smhip_runs), pointers that are not
+ * aligned to their element, a result overlapping another result, s, order or the count word (values, index and counts are taken as
+ * min(capacity, n) items, inverse as n).  n == 0: nothing is launched and the count is 0.  Asynchronous, stream-ordered; recorded tiny
+ * operators are flushed first. */
+#define SMHIP_RUNS_NAN_DISTINCT 1 /* flags: a NaN starts a run of its own (np.unique(equal_nan=False)) */
+int smhip_runs_count(int flags, int dtype, const void *s, int64_t n, int64_t *count_dev);
+int smhip_runs(int flags, int dtype, const void *s, int64_t n, const int64_t *order_or_null,
+               void *values_out, int64_t *index_out, int64_t *counts_out, int64_t *inverse_out,
+               int64_t capacity, int64_t *count_dev_or_null);
+/* Host only, no device touched: the route a call over n elements would take.  `outputs` = the results wanted, SMHIP_RUNS_* ORed
+ * (with a capacity > 0); 0 stands for smhip_runs_count.  *route = SMHIP_RUNS_ROUTE_*; *launches = the kernel launches of the call:
+ * ONE 1; TILES 2 for the count, 3 for results, 4 when SMHIP_RUNS_COUNTS is among them; info3 = {tiles, the elements of a tile for
+ * this element type, the largest n that takes the one-workgroup route}.  Any output may be NULL.  The planner's test hook. */
+#define SMHIP_RUNS_VALUES 1
+#define SMHIP_RUNS_INDEX 2
+#define SMHIP_RUNS_COUNTS 4
+#define SMHIP_RUNS_INVERSE 8
+#define SMHIP_RUNS_ROUTE_NONE 0  /* no elements: nothing to launch */
+#define SMHIP_RUNS_ROUTE_ONE 1   /* one workgroup walks the tiles with a carry, one launch */
+#define SMHIP_RUNS_ROUTE_TILES 2 /* a count per tile, their prefix, the writes, and the lengths when asked for */
+int smhip_runs_plan(int flags, int dtype, int64_t n, int outputs, int *route, int *launches, int64_t *info3);
+
 /* ----------------------------------------------------------- multi-GPU */
 /* The reference's only fan-out is the OpenMP `parallel for` over chunks of the output (calculate.h:47, :152).  Its
  * MI355X counterpart is the RESULT's outermost dimension cut into one block per GPU of the node: elementwise blocks

@@ -78,6 +78,9 @@ SELECT_OPS = {"index": SELECT_INDEX, "coords": SELECT_COORDS, "values": SELECT_V
 # smhip_select_plan's route word: a route in the low byte, the flag above it
 SELECT_ROUTE_NONE, SELECT_ROUTE_ONE, SELECT_ROUTE_TILES, SELECT_ROUTE_DENSE = range(4)
 SELECT_COPY = 0x100
+RUNS_NAN_DISTINCT = 1  # smhip_runs' flag: a NaN is a run of its own (equal_nan=False)
+RUNS_VALUES, RUNS_INDEX, RUNS_COUNTS, RUNS_INVERSE = 1, 2, 4, 8  # smhip_runs_plan's `outputs`
+RUNS_ROUTE_NONE, RUNS_ROUTE_ONE, RUNS_ROUTE_TILES = range(3)
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -1236,6 +1239,67 @@ class Smhip:
         route, launches, info = C.c_int(0), C.c_int(0), (C.c_int64 * 4)()
         self._ck(self.c.smhip_select_plan(C.c_int(what), C.c_int(cmp), C.c_int(dtype), arr(shape), C.c_int(ndim), arr(x_strides), arr(y_strides), arr(a_strides),
                                           arr(b_strides), C.byref(route), C.byref(launches), info))
+        return route.value, launches.value, tuple(int(v) for v in info)
+
+    # -- the distinct values --------------------------------------------------------
+    def unique(self, a: DeviceArray, return_index=False, return_inverse=False, return_counts=False, equal_nan=True):
+        """np.unique(a, return_index, return_inverse, return_counts, equal_nan=equal_nan) of the row-major flattening of `a` (any view):
+        the distinct values ascending, one NaN last (every NaN with equal_nan=False), as a DeviceArray of shape (U,) holding the bits of
+        each value's FIRST occurrence -- alone, or a tuple with, in numpy's order, the int64 arrays asked for: `index` (U,) the first
+        occurrence, `inverse` of a's shape (values.take(inverse) rebuilds a), `counts` (U,).  One stable sort, the count of the runs,
+        then one emitting call.  THIS WAITS FOR THE STREAM ONCE, to learn U.  a.size >= 2^31 raises what sort() raises."""
+        if a.dtype not in DTYPES:
+            raise ValueError(f"unique: dtype {a.dtype} (f32, f64, i32 and i64 only)")
+        flat = self._flat(a)
+        order = None
+        if flat.size:
+            got = self._sort(flat, 0, False, True, return_index or return_inverse, None, None)
+            flat, order = got if isinstance(got, tuple) else (got, None)
+        return self._runs(flat, order, a.shape, return_index, return_inverse, return_counts, equal_nan)
+
+    def unique_consecutive(self, a: DeviceArray, return_inverse=False, return_counts=False, equal_nan=True):
+        """torch.unique_consecutive / run-length encoding of the row-major flattening of `a`: the first element of every run of adjacent
+        elements that are the same (-0.0 == +0.0; NaNs the same among themselves unless equal_nan=False), shape (U,) -- alone, or a tuple
+        with `inverse` (a's shape: the run each element lies in) and / or `counts` (U,: the runs' lengths).  No sort, no size limit.
+        THIS WAITS FOR THE STREAM ONCE, to learn U."""
+        if a.dtype not in DTYPES:
+            raise ValueError(f"unique_consecutive: dtype {a.dtype} (f32, f64, i32 and i64 only)")
+        return self._runs(self._flat(a), None, a.shape, False, return_inverse, return_counts, equal_nan)
+
+    def _runs(self, flat, order, shape, want_index, want_inverse, want_counts, equal_nan):
+        """Count the runs of `flat` (dense, 1-D), read the count back, allocate exactly, emit."""
+        flags, dt, n = C.c_int(0 if equal_nan else RUNS_NAN_DISTINCT), C.c_int(DTYPES[flat.dtype]), flat.size
+        total = 0
+        if n:
+            word = self.empty((1,), np.int64)
+            self._ck(self.c.smhip_runs_count(flags, dt, C.c_void_p(flat.ptr), C.c_int64(n), C.c_void_p(word.ptr)))
+            total = self.read_i64(word.ptr)   # waits for the stream
+        values = self.empty((total,), flat.dtype)
+        index = self.empty((total,), np.int64) if want_index else None
+        inverse = self.empty(shape, np.int64) if want_inverse else None
+        counts = self.empty((total,), np.int64) if want_counts else None
+        if n:
+            ptr = lambda d: C.c_void_p(d.ptr if d is not None else 0)  # noqa: E731
+            self._ck(self.c.smhip_runs(flags, dt, C.c_void_p(flat.ptr), C.c_int64(n), ptr(order), ptr(values), ptr(index), ptr(counts), ptr(inverse),
+                                       C.c_int64(total), None))
+        out = (values,) + tuple(r for r in (index, inverse, counts) if r is not None)
+        return out[0] if len(out) == 1 else out
+
+    def runs_count_raw(self, flags, dtype, s_ptr, n, count_ptr):
+        """smhip_runs_count with every argument as given (argument-validation tests)."""
+        return self.c.smhip_runs_count(C.c_int(flags), C.c_int(dtype), C.c_void_p(s_ptr), C.c_int64(n), C.c_void_p(count_ptr))
+
+    def runs_raw(self, flags, dtype, s_ptr, n, order_ptr, values_ptr, index_ptr, counts_ptr, inverse_ptr, capacity, count_ptr=0):
+        """smhip_runs with every argument as given; a pointer of 0 is NULL."""
+        return self.c.smhip_runs(C.c_int(flags), C.c_int(dtype), C.c_void_p(s_ptr), C.c_int64(n), C.c_void_p(order_ptr), C.c_void_p(values_ptr),
+                                 C.c_void_p(index_ptr), C.c_void_p(counts_ptr), C.c_void_p(inverse_ptr), C.c_int64(capacity), C.c_void_p(count_ptr))
+
+    def runs_plan(self, dtype, n, outputs=RUNS_VALUES, flags=0):
+        """smhip_runs_plan (host only): (route, launches, (tiles, elements per tile, the largest n of the one-workgroup route)) for the
+        results in `outputs` (RUNS_* ORed; 0: the count alone) over n elements."""
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        route, launches, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)()
+        self._ck(self.c.smhip_runs_plan(C.c_int(flags), C.c_int(dtype), C.c_int64(n), C.c_int(outputs), C.byref(route), C.byref(launches), info))
         return route.value, launches.value, tuple(int(v) for v in info)
 
     def sum(self, a: DeviceArray):

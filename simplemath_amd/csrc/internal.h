@@ -273,4 +273,8 @@ int launch_bincount(int mode, int dtype, const void *ids, const int64_t *shape, 
 int launch_histogram(int flags, int dtype, const void *x, const int64_t *shape, const int64_t *strides, int ndim, const void *edges, int64_t bins, double lo, double hi,
                      int64_t *counts, hipStream_t s);
 
+// select.hip: the exclusive prefix of per-tile counts in ONE workgroup (offsets, when given) and their sum (*total, when given), exact in
+// int64; unique.hip's compaction runs the same launch between its count and its emit.
+int launch_tile_scan(const int32_t *counts, int64_t tiles, int64_t *offsets, int64_t *total, hipStream_t s);
+
 }  // namespace smhip

@@ -514,6 +514,14 @@ int launch_select(int what, int cmp, int dtype, const void *x, const int64_t *sx
 }
 
 }  // namespace
+
+// The prefix kernel for the other compaction built on tile counts (unique.hip).
+int launch_tile_scan(const int32_t *counts, int64_t tiles, int64_t *offsets, int64_t *total, hipStream_t s) {
+    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(axis_plan::kBlock), 0, s, counts, tiles, offsets, total);
+    SMHIP_LAUNCH_CHECK("tile prefix");
+    return SMHIP_OK;
+}
+
 }  // namespace smhip
 
 using namespace smhip;
