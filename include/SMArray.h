@@ -1191,6 +1191,25 @@ public:
     SMArray operator-() const & { return unary_of(*this, false, SMHIP_UNARY_NEG); }
     SMArray operator-() && { return unary_of(*this, true, SMHIP_UNARY_NEG); }
 
+    // CHANGING THE ELEMENT TYPE (np.ndarray.astype): a.astype<U>() / sm::astype<U>(a), T and U each float, double, int or
+    // std::int64_t.  A new dense array of a's shape in HBM, converted on the device by ONE library call (smhip_convert; smhip.h has the
+    // table): integers round to nearest even once, i64 -> i32 wraps, and float -> integer is SATURATING TRUNCATION -- toward zero, the
+    // target's min / max beyond its range, 0 for a NaN (numpy leaves that case undefined).  A view is passed with its strides; a
+    // pending chain, as in (a * b).astype<double>(), is evaluated first; U == T gives a dense copy, as numpy's astype does.  The
+    // result feeds the next chain like any device-born array; no host mirror is touched.  Asynchronous.
+    template <typename U>
+    SMArray<U> astype() const {
+        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "astype: the array's element type must be float, double, int or std::int64_t");
+        static_assert(hip::dtype_of<U>::id >= 0 && hip::dtype_of<U>::id <= SMHIP_I64, "astype<U>: U must be float, double, int or std::int64_t");
+        hip::DeviceGuard on(device());
+        const T *in = device_data();  // a pending chain that produces this operand runs here
+        SMArray<U> out = SMArray<U>::device_empty(std::vector<std::size_t>(_shape));
+        if (_shape.empty() || totalSize == 0) return out;
+        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
+        hip::check(smhip_convert(hip::dtype_of<T>::id, hip::dtype_of<U>::id, in, st.data(), sh.data(), static_cast<int>(sh.size()), out.device_data_mut()));
+        return out;
+    }
+
 private:
     // x Op y (y == nullptr: x Op scalar), recorded rather than launched when it can be part of a one-pass chain: built-in
     // + - * / on an element type with kernels.  See "deferred operator chains" at the top of this file.

@@ -328,6 +328,11 @@ SMArray<T> &index_add(SMArray<T> &arr, const SMArray<std::int64_t> &ids, const V
     return arr.index_add(ids, values, axis, mode, unique);
 }
 
+// astype<U>(a): np.ndarray.astype between float, double, int and std::int64_t, on the device (SMArray::astype, smhip_convert).  Float to
+// integer is saturating truncation: toward zero, the target's min / max beyond its range, 0 for a NaN.
+template <typename U, typename T>
+SMArray<U> astype(const SMArray<T> &a) { return a.template astype<U>(); }
+
 // Counting (np.searchsorted, np.bincount, np.histogram); the results are SMArray<std::int64_t> on the device.  searchsorted: for every
 // element of x its place among the ascending 1-D `edges` (side::left: at an equal edge's first copy, side::right: after its last).
 // bincount: how many of the int / std::int64_t `ids` name each of nbins positions, the same bits as index_add of 1 onto zeros in every

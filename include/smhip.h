@@ -284,6 +284,44 @@ int smhip_unary(int fn, int dtype, const void *a, const int64_t *strides, const 
  * the result.  Either way the bits are those of smhip_unary applied to the materialised value. */
 #define SMHIP_OP_UNARY_BASE 16
 
+/* ------------------------------------------------ changing the element type */
+/* out = dst_dtype(a), elementwise: np.ndarray.astype between f32, f64, i32 and i64 (the reference has none).  The contract:
+ *   from -> to                       rule
+ *   i32 -> i64                       sign extension
+ *   i64 -> i32                       the low 32 bits (wraps, as numpy)
+ *   i32 -> f64                       exact
+ *   i32 -> f32, i64 -> f64 / f32     round to nearest, ties to even, rounded ONCE (i64 -> f32 does not go through double:
+ *                                    2^60 + 2^36 + 1 gives 2^60 + 2^37)
+ *   f32 -> f64                       exact; subnormals and the sign of zero are kept
+ *   f64 -> f32                       round to nearest even; overflow gives +-inf; results below the normal range are the
+ *                                    correct subnormals (no flush to zero)
+ *   f32 / f64 -> i32 / i64           SATURATING TRUNCATION: toward zero; a value whose truncation lies outside the target's
+ *                                    range gives the target's min / max; NaN gives 0; -0.0 and -0.9 give 0
+ * Float to float, a NaN converts to a NaN (sign and payload not specified).  Saturating truncation is Rust's `as`, Java's
+ * cast and WebAssembly's trunc_sat; numpy and C leave the out-of-range case undefined (numpy on x86 returns INT_MIN for all
+ * of it), so there -- and only there -- the result differs from what numpy happens to return.  The functions themselves:
+ * csrc/sm_convert.h, compiled for host and device alike; deterministic.
+ * `a` is any view: `strides` (ELEMENTS, >= 0; 0 broadcasts) over `shape`, rank 1..SMHIP_MAX_NDIM, exactly as smhip_unary
+ * takes it; `out` is dense row-major over `shape` in dst_dtype.  Routes (smhip_convert_plan reports the one a call takes):
+ *   DENSE   a dense operand (a slice that starts at any element included): one pass, sizeof(S) + sizeof(D) bytes per element
+ *   ROWS    a view whose innermost stride is 1 -- a block of rows or columns, an outer axis broadcast: read in place, the same traffic
+ *   STAGED  any other view (transposed, stepped or broadcast along the last axis): copied dense in the source type into a
+ *           pooled block, then converted: 3 * sizeof(S) + sizeof(D) bytes per element
+ *   COPY    src_dtype == dst_dtype: a dense copy of the view, 2 * sizeof(S) bytes per element
+ * Any overlap of `out` with the operand's span is SMHIP_ERR_INVALID.  A bad dtype or ndim, a negative extent or stride, or a
+ * null pointer with a non-empty shape is SMHIP_ERR_INVALID, checked before any device is touched.  An empty shape is a no-op.
+ * Asynchronous, stream-ordered like the other operators; results of <= 4096 elements are not recorded in the tiny batch but
+ * run at once, behind everything that is recorded. */
+typedef enum smhip_convert_route {
+    SMHIP_CONVERT_ROUTE_NONE = 0, SMHIP_CONVERT_ROUTE_DENSE = 1, SMHIP_CONVERT_ROUTE_ROWS = 2, SMHIP_CONVERT_ROUTE_STAGED = 3,
+    SMHIP_CONVERT_ROUTE_COPY = 4
+} smhip_convert_route;
+int smhip_convert(int src_dtype, int dst_dtype, const void *a, const int64_t *strides, const int64_t *shape, int ndim, void *out);
+/* Host only, no device touched: the route, the number of kernel launches (pieces counted; STAGED's copy as one) and the bytes
+ * moved, from the planner the launch itself uses.  An empty shape: NONE, 0, 0.  Any of the three may be NULL. */
+int smhip_convert_plan(int src_dtype, int dst_dtype, const int64_t *shape, const int64_t *strides, int ndim, int *route, int *launches,
+                       int64_t *bytes_moved);
+
 /* ------------------------------------------------------- axis reductions */
 /* np.sum / np.mean / np.max / np.min over chosen axes (the reference reduces only whole arrays: product.h).  The contract:
  *   kind   f32                                   f64                i32 / i64

@@ -81,6 +81,7 @@ SELECT_COPY = 0x100
 RUNS_NAN_DISTINCT = 1  # smhip_runs' flag: a NaN is a run of its own (equal_nan=False)
 RUNS_VALUES, RUNS_INDEX, RUNS_COUNTS, RUNS_INVERSE = 1, 2, 4, 8  # smhip_runs_plan's `outputs`
 RUNS_ROUTE_NONE, RUNS_ROUTE_ONE, RUNS_ROUTE_TILES = range(3)
+CONVERT_ROUTE_NONE, CONVERT_ROUTE_DENSE, CONVERT_ROUTE_ROWS, CONVERT_ROUTE_STAGED, CONVERT_ROUTE_COPY = range(5)  # smhip_convert_route
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -378,6 +379,51 @@ class Smhip:
         return self.c.smhip_unary(C.c_int(fn), C.c_int(dtype), C.c_void_p(a_ptr), _i64(strides) if strides is not None else None,
                                   _i64(shape) if shape is not None else None, C.c_int(len(shape) if shape is not None else 0),
                                   C.c_void_p(out_ptr))
+
+    # -- changing the element type ------------------------------------------------------
+    @staticmethod
+    def _convert_dtype(dtype, who):
+        try:
+            dt = np.dtype(dtype)
+        except TypeError as e:
+            raise TypeError(f"{who}: {dtype!r} is not an element type") from e
+        if dt not in DTYPES:
+            raise TypeError(f"{who}: element type {dt} is not one of float32, float64, int32, int64")
+        return dt
+
+    def astype(self, a: DeviceArray, dtype, out: DeviceArray | None = None):
+        """np.ndarray.astype on the device between float32, float64, int32 and int64 (smhip_convert; smhip.h has the rules: float to
+        integer is saturating truncation, NaN gives 0).  `a` any view -> a new dense DeviceArray of a's shape, or into `out`, which
+        must be a dense array of `dtype` and a's shape and must not overlap `a`.  The same dtype gives a dense copy."""
+        dt = self._convert_dtype(dtype, "astype")
+        self._convert_dtype(a.dtype, "astype")
+        if out is None:
+            out = self.empty(a.shape, dt)
+        elif out.dtype != dt:
+            raise TypeError(f"astype: out is {out.dtype}, the result is {dt}")
+        elif tuple(out.shape) != tuple(a.shape) or not out.is_dense():
+            raise ValueError(f"astype: out must be a dense array of shape {tuple(a.shape)}; got {tuple(out.shape)} dense={out.is_dense()}")
+        self._ck(self.c.smhip_convert(C.c_int(DTYPES[a.dtype]), C.c_int(DTYPES[dt]), C.c_void_p(a.ptr), _i64(a.strides), _i64(a.shape),
+                                      C.c_int(a.ndim), C.c_void_p(out.ptr)))
+        return out
+
+    def convert_raw(self, src_dtype, dst_dtype, a_ptr, strides, shape, out_ptr):
+        """smhip_convert with every argument as given (argument-validation tests)."""
+        return self.c.smhip_convert(C.c_int(src_dtype), C.c_int(dst_dtype), C.c_void_p(a_ptr), _i64(strides) if strides is not None else None,
+                                    _i64(shape) if shape is not None else None, C.c_int(len(shape) if shape is not None else 0),
+                                    C.c_void_p(out_ptr))
+
+    def convert_plan(self, src_dtype, dst_dtype, shape, strides, ndim=None):
+        """smhip_convert_plan (host only): (route, launches, bytes moved) for converting a view of these shape and strides (elements)."""
+        src_dtype = DTYPES[self._convert_dtype(src_dtype, "convert_plan")] if not isinstance(src_dtype, int) else src_dtype
+        dst_dtype = DTYPES[self._convert_dtype(dst_dtype, "convert_plan")] if not isinstance(dst_dtype, int) else dst_dtype
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        arr = lambda v: _i64(v) if v is not None else None  # noqa: E731
+        route, launches, moved = C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._ck(self.c.smhip_convert_plan(C.c_int(src_dtype), C.c_int(dst_dtype), arr(shape), arr(strides), C.c_int(ndim), C.byref(route),
+                                           C.byref(launches), C.byref(moved)))
+        return route.value, launches.value, moved.value
 
     @staticmethod
     def _stage(st):
