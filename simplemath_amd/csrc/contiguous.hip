@@ -15,11 +15,15 @@
 //     grid-stride variants with 2-8 vectors in flight per lane measured
 //     5-12 % slower on this 2R+1W stream;
 //   - non-temporal loads and stores (each byte is touched once): +8 %.
-// Blocks are dealt round-robin over the 8 XCDs, consecutive blocks touch
-// consecutive 16 KiB spans, so every XCD streams from all HBM stacks at once;
-// there is no reuse for an XCD-affine mapping to exploit.
+// Blocks are dealt round-robin over the 8 XCDs.  In natural order consecutive
+// blocks touch consecutive 16 KiB spans, so each XCD reads every eighth span;
+// there is no reuse for an XCD-affine mapping to exploit, but there is
+// locality: in the launches of an operand above 512 MiB each XCD takes 32
+// consecutive spans out of every 256 (front_order.h), which is worth 1-2 %
+// there and nothing below (profiles/sweep_fronts.txt).
 #include <type_traits>
 
+#include "front_order.h"
 #include "internal.h"
 #include "ops.hip.h"
 
@@ -39,14 +43,16 @@ constexpr size_t kBigThreshold = (size_t)1 << 20;
 // KEEP_STORES: the write side's policy (ops.hip.h) at compile time -- a run-time branch in front of this kernel's one
 // store cost the N = 2^28 add 1.6 % (498 -> 507 us, same box, tools/op_matrix.py); the 1R+1W scalar kernels below do not
 // notice theirs.
+// order: log2 C of front_order.h's walk, 0 = natural order -- scalar arithmetic on blockIdx.x ahead of the loads.  A bijection
+// on the launch's workgroups that leaves the block of the i == n_vec tail thread where it is.
 template <typename T, typename Op, int BLOCK, bool KEEP_STORES>
 __global__ __launch_bounds__(BLOCK) void contiguous_vec_kernel(const T *__restrict__ a, const T *__restrict__ b,
-                                                               T *__restrict__ out, size_t n_vec, int tail, int nt) {
+                                                               T *__restrict__ out, size_t n_vec, int tail, int nt, int order) {
     typedef typename VecTraits<T>::vec_t V;
     constexpr int W = VecTraits<T>::width;
     OpCtx<Op> ctx;
     ctx.init();
-    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    const size_t i = (size_t)front_tile(blockIdx.x, (unsigned)order, (unsigned)(n_vec / BLOCK)) * BLOCK + threadIdx.x;
     if (i < n_vec) {
         const V va = load_stream_if(T, reinterpret_cast<const V *>(a) + i, nt);
         const V vb = load_stream_if(T, reinterpret_cast<const V *>(b) + i, nt);
@@ -261,11 +267,17 @@ template <int KIND> struct HeavyTile<double, KIND> { static constexpr int value 
 // instead of 2 % -- and runs 2 % FASTER (tools/sweep_vmm.hip, tools/pmc_vmm.sh -> profiles/r03_pmc_vmm.txt); the distance
 // between the three streams does nothing either (tools/sweep_distance.hip).  What matters is the launch's LENGTH: the same
 // 12 GiB, same placement, as four launches of 2^28 run at 79.9 %, as sixteen of 2^26 at 80.7 % (one launch: 78.0 %).  A
-// launch's workgroups are dealt to the eight XCDs in order and each XCD works through its share at its own pace; over
-// hundreds of thousands of workgroups their fronts drift apart and the DRAM pages they share stop being open for each
-// other; a kernel boundary lines them up again.  So: pieces of 2^24 vectors (256 MiB per operand) once an operand
-// exceeds 1 GiB -- and, found later, even the headline's 1 GiB operands gain 1 % from going out as TWO launches
-// (internal.h: piece_for has the rule and its numbers).
+// launch's workgroups are dealt to the eight XCDs in order and each XCD works through its share at its own pace.  Seen
+// directly (every workgroup stamping wall_clock64() at entry, tools/sweep_fronts.hip -> profiles/front_drift.txt): four of
+// the eight classes blockIdx.x % 8 run about 5 % ahead of the other four from the first microseconds on, so the distance
+// between the fastest and the slowest front grows linearly with the launch -- 12-20 MiB of each stream at the end of a
+// 256 MiB launch, 37-49 MiB at 1 GiB, 160-200 MiB at 4 GiB -- and a kernel boundary lines them up again (halves of 1 GiB:
+// 26 MiB; pieces of 256 MiB: 18-31 MiB).  So: pieces of 2^24 vectors (256 MiB per operand) once an operand exceeds 1 GiB
+// -- and, found later, even the headline's 1 GiB operands gain 1 % from going out as TWO launches (internal.h: piece_for
+// has the rule and its numbers).  Pieces staggered over two queues, so that one queue's drain hides behind the other's
+// running piece, lose 1-6 % to running two long kernels side by side.  Inside the pieces run_contiguous and the fused op+sum
+// let each XCD take 32 consecutive tiles out of every 256 (front_order.h): the fronts drift exactly as before, and the add
+// gains 1-2 % all the same -- what that order buys is longer runs of one XCD in the same DRAM pages, not closer fronts.
 
 // Half-integer exponents whose double-double product chain (sm_pow64.h: pow_halfint_n) is slower than the one-exponent exp(s log a)
 inline bool m2_is_slow_chain(double s) {
@@ -366,24 +378,26 @@ int run_contiguous(const void *a, const void *b, void *out, size_t n, hipStream_
         launch_heavy<T, Op, 0>(pa, pb, T{}, po, n_vec, tail, s);
     } else if (const size_t piece = piece_for(n_vec, 3)) {
         const int pol = stream_policy({{pa, n * sizeof(T)}, {pb, n * sizeof(T)}}, {po, n * sizeof(T)});  // above the cache: nt both ways
+        const int order = front_order_for(n_vec, 3);  // each piece walks its tiles in front_order.h's order
         for (size_t v0 = 0; v0 < n_vec || (v0 == n_vec && tail); v0 += piece) {
             const bool last = v0 + piece >= n_vec;
             const size_t nv = last ? n_vec - v0 : piece;
             if (int rc = grid_for(nv + (last && tail ? 1 : 0), kBlockBig, &grid)) return rc;
             hipLaunchKernelGGL((contiguous_vec_kernel<T, Op, kBlockBig, false>), dim3(grid), dim3(kBlockBig), 0, s, pa + v0 * W, pb + v0 * W, po + v0 * W, nv,
-                               last ? tail : 0, pol & ~kStoreKeep);
+                               last ? tail : 0, pol & ~kStoreKeep, order);
             if (last) break;
         }
     } else if (n_vec >= kBigThreshold) {
         if (int rc = grid_for(threads, kBlockBig, &grid)) return rc;
         const int pol = stream_policy({{pa, n * sizeof(T)}, {pb, n * sizeof(T)}}, {po, n * sizeof(T)});
-        if (pol & kStoreKeep) hipLaunchKernelGGL((contiguous_vec_kernel<T, Op, kBlockBig, true>), dim3(grid), dim3(kBlockBig), 0, s, pa, pb, po, n_vec, tail, pol);
-        else hipLaunchKernelGGL((contiguous_vec_kernel<T, Op, kBlockBig, false>), dim3(grid), dim3(kBlockBig), 0, s, pa, pb, po, n_vec, tail, pol);
+        const int order = front_order_for(n_vec, 3);  // 0 but under the test override: one launch is short enough for natural order
+        if (pol & kStoreKeep) hipLaunchKernelGGL((contiguous_vec_kernel<T, Op, kBlockBig, true>), dim3(grid), dim3(kBlockBig), 0, s, pa, pb, po, n_vec, tail, pol, order);
+        else hipLaunchKernelGGL((contiguous_vec_kernel<T, Op, kBlockBig, false>), dim3(grid), dim3(kBlockBig), 0, s, pa, pb, po, n_vec, tail, pol, order);
     } else {
         if (int rc = grid_for(threads, kBlockSmall, &grid)) return rc;
         // below kBigThreshold vectors (16 MiB per operand: 48 MiB in all at most) a footprint above the keep-store floor
         // is a corner this form does not serve
-        hipLaunchKernelGGL((contiguous_vec_kernel<T, Op, kBlockSmall, false>), dim3(grid), dim3(kBlockSmall), 0, s, pa, pb, po, n_vec, tail, stream_policy({{pa, n * sizeof(T)}, {pb, n * sizeof(T)}}, {po, n * sizeof(T)}) & ~kStoreKeep);
+        hipLaunchKernelGGL((contiguous_vec_kernel<T, Op, kBlockSmall, false>), dim3(grid), dim3(kBlockSmall), 0, s, pa, pb, po, n_vec, tail, stream_policy({{pa, n * sizeof(T)}, {pb, n * sizeof(T)}}, {po, n * sizeof(T)}) & ~kStoreKeep, 0);
     }
     SMHIP_LAUNCH_CHECK("contiguous");
     return SMHIP_OK;

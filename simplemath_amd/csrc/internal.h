@@ -143,13 +143,24 @@ void residency_forget(int dev, const void *p, size_t bytes);
 //                   2^25 < n_vec <= 2^26 (1 GiB)   halves of 2^25: the headline's 2^28 floats as TWO launches, 496.6 -> 491.8 us
 //                                                  (81.1 -> 81.9 %, five alternating rounds each within 0.1 %; four pieces 81.6, eight 80.7 %)
 //                   larger                         pieces of 2^24 (256 MiB): 2^29 80.0 -> 82.6 %, 2^30 78.4 -> 81.5 %, 2^31 76-81 -> 82-83 %
-//   one / two       n_vec <= 2^27 (2 GiB)          one launch (pieces change nothing up to there: a*s 81.4 / 81.5 %, sum 83.2 / 83.4 %,
+//                                                  Measured again with front_order.h's walk inside the pieces (front_order_for below;
+//                                                  profiles/sweep_fronts.txt): 2^28 floats whole / halves / quarters / eighths 82.7 / 83.3 /
+//                                                  83.2 / 82.0 %, 2^30 floats in pieces of 2^23 / 2^24 / 2^25 81.9 / 83.2 / 83.3 % (natural
+//                                                  order: 80.7 / 81.9 / 82.2 %) -- 2^24 and 2^25 are level in either order, so the rule stays
+//   one / two      n_vec <= 2^27 (2 GiB)          one launch (pieces change nothing up to there: a*s 81.4 / 81.5 %, sum 83.2 / 83.4 %,
 //                                                  dot 83.3 / 82.0 % whole / in pieces at 2^28-2^29 elements)
 //                   larger                         pieces of 2^25: a*s 80.5 -> 81.2 %, sum 82.1 -> 83.7 %, dot 80.9 -> 82.7 % at 2^30
-//   (profiles/r03_headline_pieces.txt, r03_mid_pieces.txt, r03_big_add.txt, r03_mix_pieces.txt)
+//   (profiles/r03_headline_pieces.txt, r03_mid_pieces.txt, r03_big_add.txt, r03_mix_pieces.txt, sweep_fronts.txt)
 // SMHIP_PIECE_LOG2VEC=<k>: every operand above 2^k vectors in pieces of 2^k, whatever the mix (tests run the piece loops at
 // small sizes with it); 0: never split.
 size_t piece_for(size_t n_vec, int streams);
+// The order in which a launch of contiguous_vec_kernel, or of the fused op+sum's reduce_kernel, walks its tiles
+// (front_order.h): log2 C, 0 = natural order.  C = 32 for the launches of a three-stream operand that goes out in pieces
+// (n_vec > 2^25), natural order below: at 2^24 vectors the new order's gain is inside the noise (83.05 -> 83.39 % against a
+// spread of 0.9 points, profiles/sweep_fronts.txt).  The one- and two-stream kernels keep natural order.
+// SMHIP_FRONT_LOG2C=<k>, k = 1 .. 8 (read once, tests only): C = 2^k for EVERY launch of those two kernels' 1024-thread
+// forms, in pieces or not, so that the order is live at test sizes.
+int front_order_for(size_t n_vec, int streams);
 
 inline size_t dtype_size(int dtype) {
     switch (dtype) {

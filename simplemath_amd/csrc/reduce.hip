@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "front_order.h"
 #include "internal.h"
 #include "ops.hip.h"
 #include "wave.hip.h"
@@ -165,7 +166,7 @@ constexpr int block_of(int mode) { return mode == 2 /* kFused */ ? SMHIP_FUSED_B
 template <typename T, typename Op, int MODE, bool KEEP, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void reduce_kernel(const T *__restrict__ a, const T *__restrict__ b, T *__restrict__ out,
                                                            size_t n_vec, size_t n, typename AccOf<T>::type *__restrict__ partials,
-                                                           void *__restrict__ out8, T *__restrict__ out_native, int nt, int single) {
+                                                           void *__restrict__ out8, T *__restrict__ out_native, int nt, int single, int order) {
     typedef typename AccOf<T>::type A;
     typedef typename VecTraits<T>::vec_t V;
     constexpr int W = VecTraits<T>::width;
@@ -173,11 +174,15 @@ __global__ __launch_bounds__(BLOCK) void reduce_kernel(const T *__restrict__ a, 
     constexpr size_t kTile = (size_t)BLOCK * kVecPerThread;
     const V *av = reinterpret_cast<const V *>(a), *bv = reinterpret_cast<const V *>(b);
     V *ov = reinterpret_cast<V *>(out);
-    const size_t tile0 = (size_t)blockIdx.x * kTile + threadIdx.x;
+    // the fused op+sum walks its tiles like the contiguous kernel (front_order.h; order = log2 C, 0 = natural): workgroup
+    // blockIdx.x takes tile `blk` and writes partial `blk`, so the partials, their order and the sum's bits stay what they
+    // were; the last workgroup (partial tile + tail) keeps its place
+    const unsigned blk = MODE == kFused ? front_tile(blockIdx.x, (unsigned)order, (unsigned)(n_vec / kTile)) : blockIdx.x;
+    const size_t tile0 = (size_t)blk * kTile + threadIdx.x;
     OpCtx<Op> ctx;
     ctx.init();
     A acc = A(0);
-    if ((size_t)blockIdx.x * kTile + kTile <= n_vec) {
+    if ((size_t)blk * kTile + kTile <= n_vec) {
         V va[kVecPerThread], vb[kVecPerThread];
         // a branch per load, as round 2 had it: grouped under one branch this kernel measured 2 us SLOWER (497.5-498.5 against
         // 495.6-496.5 us, tools/sweep_fused2.hip -> profiles/r03_sweep_fused2.txt) -- the opposite of the strided-row kernel's
@@ -200,7 +205,7 @@ __global__ __launch_bounds__(BLOCK) void reduce_kernel(const T *__restrict__ a, 
             }
         }
         // scalar tail (n % W elements): the last workgroup's first lane
-        if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        if (blk == gridDim.x - 1 && threadIdx.x == 0) {
             for (size_t k = n_vec * W; k < n; ++k) {
                 if constexpr (MODE == kFused) {
                     const T r = Op::apply(a[k], b[k]);
@@ -214,7 +219,7 @@ __global__ __launch_bounds__(BLOCK) void reduce_kernel(const T *__restrict__ a, 
     acc = block_reduce<A, BLOCK>(acc);
     if (threadIdx.x == 0) {
         if (single) write_result<T, MODE != kDot>(acc, out8, out_native);  // a small array (one workgroup in all): no second launch
-        else partials[blockIdx.x] = acc;
+        else partials[blk] = acc;
     }
 }
 
@@ -656,6 +661,7 @@ int run_reduce(const void *a_, const void *b_, void *out_, size_t n, void *out8,
     const size_t piece = piece_for(n_vec, MODE == kSum ? 1 : MODE == kDot ? 2 : 3);
     const size_t piece_tiles = piece ? (piece / tile ? piece / tile : 1) : blocks;
     const size_t full_tiles = blocks - 1;  // the last workgroup of the whole array is the partial tile + tail: it rides with the last piece
+    const int order = MODE == kFused ? front_order_for(n_vec, 3) : 0;  // the fused op+sum's pieces walk their tiles like the contiguous kernel's
     for (size_t b0 = 0; b0 < blocks;) {
         const bool last = b0 + piece_tiles >= full_tiles;
         const size_t nb = last ? blocks - b0 : piece_tiles;
@@ -667,10 +673,10 @@ int run_reduce(const void *a_, const void *b_, void *out_, size_t n, void *out8,
         A *pp = partials ? partials + b0 : partials;
         if (keep)
             hipLaunchKernelGGL((reduce_kernel<T, Op, MODE, MODE == kFused, BLOCK>), dim3((unsigned)nb), dim3(BLOCK), 0, s, pa, pb, po, nv, ne, pp, out8,
-                               static_cast<T *>(out_native), pol, blocks == 1 ? 1 : 0);
+                               static_cast<T *>(out_native), pol, blocks == 1 ? 1 : 0, order);
         else
             hipLaunchKernelGGL((reduce_kernel<T, Op, MODE, false, BLOCK>), dim3((unsigned)nb), dim3(BLOCK), 0, s, pa, pb, po, nv, ne, pp, out8,
-                               static_cast<T *>(out_native), pol, blocks == 1 ? 1 : 0);
+                               static_cast<T *>(out_native), pol, blocks == 1 ? 1 : 0, order);
         b0 += nb;
     }
     SMHIP_LAUNCH_CHECK("reduce");

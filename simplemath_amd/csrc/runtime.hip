@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "front_order.h"
 #include "internal.h"
 
 namespace smhip {
@@ -571,6 +572,16 @@ size_t piece_for(size_t n_vec, int streams) {
         return 0;
     }
     return n_vec > ((size_t)1 << 27) ? (size_t)1 << 25 : 0;
+}
+
+int front_order_for(size_t n_vec, int streams) {
+    static const int forced = [] {  // 0: the built-in rule; k: C = 2^k for every launch of the 1024-thread kernel (tests)
+        const char *e = getenv("SMHIP_FRONT_LOG2C");
+        const long k = e ? atol(e) : 0;
+        return k <= 0 ? 0 : (k > (long)kFrontMaxLog2C ? (int)kFrontMaxLog2C : (int)k);
+    }();
+    if (forced) return forced;
+    return streams >= 3 && n_vec > ((size_t)1 << 25) ? (int)kFrontLog2C : 0;
 }
 
 hipEvent_t pool_event_take(int dev) { return take_event(dev); }
