@@ -7,6 +7,7 @@
 
 #include <initializer_list>
 
+#include "queue_order.h"
 #include "smhip.h"
 
 namespace smhip {
@@ -33,7 +34,6 @@ void tiny_stats(int dev, unsigned long long *launches, unsigned long long *opera
 // Second library queue of `dev` off (true) / on again (false); see runtime.hip "two queues per device".
 void dispatch_single_queue(int dev, bool single);
 
-struct Span { const void *p; size_t bytes; };
 // One operator of the C ABI: which library queue it runs on and what it is ordered behind (runtime.hip: two queues per
 // device).  begin() with the operator's operand spans lets independent operators overlap; begin_barrier() is for entry
 // points whose spans are not declared: ordered behind everything, everything later behind them.  The scope keeps the

@@ -253,30 +253,12 @@ int order_after(Tag &tag, int dev, hipStream_t s) {
 // orders itself behind; the caller's own stream (smhip_set_stream) is outside all this -- operators run there in the
 // order they were called, as before -- and a caller that takes the library's stream handle (smhip_get_stream) or drives
 // the device group (sharded entry points) turns the second queue off for that device.  SMHIP_QUEUES=1 turns it off everywhere.
-constexpr int kUses = 256;
-constexpr size_t kOverlapMinBytes = (size_t)1 << 20;   // smaller operators are barrier operators: nothing to overlap, nothing to track
-// Larger operators stay on queue 0 (tracked like the others).  Two queues do not just overlap a kernel's tail with the next
-// one's head: the hardware runs the two kernels side by side, which halves the fixed cost per launch and doubles the streams
-// the memory side sees at once.  Cold operands, % of peak with one / two queues (tools/cold_rates.py, profiles/r04_cold_rates_queues.txt):
-// a + b at 16 / 32 / 64 MiB per array 63 / 71 / 78 -> 77 / 79 / 80, at 128 / 256 MiB 80.9 / 82.5 -> 79.7 / 78.8;
-// (R, 4096) * (1, 4096) at 16 / 32 / 64 MiB 56 / 68 / 75.2 -> 65 / 74 / 75.8, at 128 MiB 79.2 -> 76.8; a * s gains up to 128 MiB.
-// (A second queue of another PRIORITY, high or low, ran like one queue: no overlap at all.)
-constexpr size_t kOverlapMaxBytes = (size_t)224 << 20;
-struct Dispatch {
+// The bookkeeping -- the span table, the choice of queue, which dependencies become edges, barriers and floors -- is plain
+// host code in queue_order.h (tests/cpp/queue_order_host.cpp checks it against a model); what stays here is the mutex, the
+// streams and the edge itself.
+struct Dispatch : QueueOrder {
     std::recursive_mutex m;
     hipStream_t q1 = nullptr;
-    uint64_t seq[2] = {0, 0};      // operators issued per queue
-    uint64_t synced[2][2] = {};    // synced[q][p]: queue q is ordered behind queue p's operators up to this one
-    uint64_t floor[2] = {0, 0};    // every later operator is ordered behind these (evicted spans, barrier operators)
-    // who last wrote / read which span: structure of arrays, so that the overlap scan of an operator (its <= 17 spans against
-    // every span on record) is a handful of vector compares
-    uintptr_t lo[kUses] = {}, hi[kUses] = {};
-    uint64_t wseq[kUses] = {}, rseq[kUses][2] = {};
-    unsigned char wq[kUses] = {};
-    int used = 0, next = 0;
-    int last = 1;                  // the queue the last independent operator took
-    bool single = false;           // second queue off (the stream handle was handed out, sharded use, SMHIP_QUEUES=1)
-    unsigned long long edges = 0, alternations = 0;  // diagnostics
 };
 Dispatch g_dispatch[kMaxDevices];
 bool queues_enabled() {
@@ -285,73 +267,23 @@ bool queues_enabled() {
 }
 hipStream_t queue_stream(int dev, int q) { return q == 0 ? g_streams[dev] : g_dispatch[dev].q1; }
 
-// Orders queue q behind queue p's operators up to `need` (no-op when it already is).  Caller holds d.m.
-int queue_wait(Dispatch &d, int dev, int q, int p, uint64_t need) {
-    if (q == p || need <= d.synced[q][p] || !queue_stream(dev, p) || !queue_stream(dev, q)) return SMHIP_OK;
-    hipEvent_t e = take_event(dev);
-    if (!e) {
-        SMHIP_TRY(hipStreamSynchronize(queue_stream(dev, p)));
-    } else {
-        hipError_t err = hipEventRecord(e, queue_stream(dev, p));
-        if (err == hipSuccess) err = hipStreamWaitEvent(queue_stream(dev, q), e, 0);
-        give_event(dev, e);
-        if (err != hipSuccess) return fail(SMHIP_ERR_HIP, "queues: ordering queue %d behind queue %d: %s", q, p, hipGetErrorString(err));
-    }
-    d.synced[q][p] = d.seq[p];  // the event covers everything queued on p so far
-    ++d.edges;
-    return SMHIP_OK;
-}
-// Queue 0 waits for everything on queue 1 and becomes the point everything later is ordered behind: what an operator
-// with undeclared spans, a read-back, a timing event or a hand-over to a caller's stream needs.  Caller holds d.m.
-int queue_barrier(Dispatch &d, int dev) {
-    if (d.q1) {
-        if (int rc = queue_wait(d, dev, 0, 1, d.seq[1])) return rc;
-    }
-    d.floor[0] = ++d.seq[0];
-    return SMHIP_OK;
-}
-// The record of span [lo, hi): the one that names exactly it, or a fresh one (what drops out of the table becomes a floor).
-int use_slot(Dispatch &d, uintptr_t lo, uintptr_t hi) {
-    for (int i = 0; i < d.used; ++i)
-        if (d.lo[i] == lo && d.hi[i] == hi) return i;
-    int i;
-    if (d.used < kUses) {
-        i = d.used++;
-    } else {
-        i = d.next;
-        d.next = (d.next + 1) % kUses;
-        if (d.wseq[i] > d.floor[d.wq[i]]) d.floor[d.wq[i]] = d.wseq[i];
-        for (int k = 0; k < 2; ++k)
-            if (d.rseq[i][k] > d.floor[k]) d.floor[k] = d.rseq[i][k];
-    }
-    d.lo[i] = lo;
-    d.hi[i] = hi;
-    d.wseq[i] = d.rseq[i][0] = d.rseq[i][1] = 0;
-    d.wq[i] = 0;
-    return i;
-}
-// What an operator that reads `reads` and writes `write` must be ordered behind, per queue -- on top of the floors, which
-// every operator is behind and which therefore say nothing about the queue that suits it.
-void dependencies(const Dispatch &d, const Span *reads, size_t n_reads, Span write, uint64_t (&need)[2]) {
-    need[0] = need[1] = 0;
-    const int n = d.used;
-    if (write.p && write.bytes) {  // WAW and WAR
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(write.p), hi = lo + write.bytes;
-        for (int i = 0; i < n; ++i) {
-            if (d.lo[i] < hi && lo < d.hi[i]) {
-                if (d.wseq[i] > need[d.wq[i]]) need[d.wq[i]] = d.wseq[i];
-                if (d.rseq[i][0] > need[0]) need[0] = d.rseq[i][0];
-                if (d.rseq[i][1] > need[1]) need[1] = d.rseq[i][1];
-            }
+// Orders queue q of device `dev` behind everything queued on its queue p so far: queue_order.h's `order`.  Caller holds
+// the dispatcher's mutex.
+struct QueueEdge {
+    int dev;
+    int operator()(int q, int p) const {
+        hipEvent_t e = take_event(dev);
+        if (!e) {
+            SMHIP_TRY(hipStreamSynchronize(queue_stream(dev, p)));
+        } else {
+            hipError_t err = hipEventRecord(e, queue_stream(dev, p));
+            if (err == hipSuccess) err = hipStreamWaitEvent(queue_stream(dev, q), e, 0);
+            give_event(dev, e);
+            if (err != hipSuccess) return fail(SMHIP_ERR_HIP, "queues: ordering queue %d behind queue %d: %s", q, p, hipGetErrorString(err));
         }
+        return SMHIP_OK;
     }
-    for (size_t r = 0; r < n_reads; ++r) {  // RAW
-        if (!reads[r].p || !reads[r].bytes) continue;
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(reads[r].p), hi = lo + reads[r].bytes;
-        for (int i = 0; i < n; ++i)
-            if (d.lo[i] < hi && lo < d.hi[i] && d.wseq[i] > need[d.wq[i]]) need[d.wq[i]] = d.wseq[i];
-    }
-}
+};
 }  // namespace
 
 // An operator's scope: picks its queue, orders it behind what it depends on, and keeps the device's dispatcher locked
@@ -376,87 +308,45 @@ int OpScope::begin(const Span *reads, size_t n_reads, Span write, hipStream_t *s
         return SMHIP_OK;
     }
     tls.op_queue = 0;
-    size_t bytes = write.bytes;
-    for (size_t i = 0; i < n_reads; ++i) bytes += reads[i].bytes;
-    if (barrier || d.single || !queues_enabled() || bytes < kOverlapMinBytes) return queue_barrier(d, dev);
-    if (!d.q1) {
-        hipStream_t q = nullptr;
-        if (hipStreamCreateWithFlags(&q, hipStreamNonBlocking) != hipSuccess) {
+    int q = 0;
+    const int rc = queue_begin(d, reads, n_reads, write, barrier, queues_enabled(), &q, QueueEdge{dev}, [&d] {
+        hipStream_t q1 = nullptr;
+        if (hipStreamCreateWithFlags(&q1, hipStreamNonBlocking) != hipSuccess) {
             (void)hipGetLastError();
-            d.single = true;
-            return queue_barrier(d, dev);
+            return false;
         }
-        d.q1 = q;
-    }
-    uint64_t need[2];
-    dependencies(d, reads, n_reads, write, need);
-    // the queue that costs no event edge; an operator that depends on nothing unfinished elsewhere takes the queue the
-    // previous such operator did not
-    const bool edge0 = need[1] > d.synced[0][1], edge1 = need[0] > d.synced[1][0];  // what running on queue 0 / 1 would have to wait for
-    int q;
-    if (bytes > kOverlapMaxBytes) q = 0;
-    else if (edge0 != edge1) q = edge0 ? 1 : 0;
-    else if (!edge0) { q = d.last ^ 1; d.last = q; ++d.alternations; }
-    else q = 0;
-    if (int rc = queue_wait(d, dev, q, q ^ 1, need[q ^ 1] > d.floor[q ^ 1] ? need[q ^ 1] : d.floor[q ^ 1])) return rc;
-    const uint64_t my = ++d.seq[q];
-    if (write.p && write.bytes) {
-        const int w = use_slot(d, reinterpret_cast<uintptr_t>(write.p), reinterpret_cast<uintptr_t>(write.p) + write.bytes);
-        d.wq[w] = (unsigned char)q;
-        d.wseq[w] = my;
-        d.rseq[w][0] = d.rseq[w][1] = 0;
-    }
-    for (size_t i = 0; i < n_reads; ++i) {
-        if (!reads[i].p || !reads[i].bytes) continue;
-        const int r = use_slot(d, reinterpret_cast<uintptr_t>(reads[i].p), reinterpret_cast<uintptr_t>(reads[i].p) + reads[i].bytes);
-        d.rseq[r][q] = my;
-    }
+        d.q1 = q1;
+        return true;
+    });
+    if (rc) return rc;
     tls.op_queue = q;
     *s = queue_stream(dev, q);
     return SMHIP_OK;
 }
 
 namespace {
-// Bytes an operator in progress allocated for itself (partial sums, written-out periods, the temporaries of a cut chain): a
-// write of that operator, ordered behind whoever used those bytes before.
+// Bytes an operator in progress allocated for itself: queue_order.h's note_scratch for the operator's queue.
 int note_scratch(void *p, size_t bytes) {
     if (tls.op_depth <= 0 || tls.use_user_stream) return SMHIP_OK;
     const int dev = tls.device;
     Dispatch &d = g_dispatch[dev];
     std::lock_guard<std::recursive_mutex> lock(d.m);
-    if (d.single || !d.q1) return SMHIP_OK;  // one queue: stream order
-    const int q = tls.op_queue;
-    uint64_t need[2];
-    dependencies(d, nullptr, 0, Span{p, bytes}, need);
-    if (int rc = queue_wait(d, dev, q, q ^ 1, need[q ^ 1] > d.floor[q ^ 1] ? need[q ^ 1] : d.floor[q ^ 1])) return rc;
-    const int w = use_slot(d, reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + bytes);
-    d.wq[w] = (unsigned char)q;
-    d.wseq[w] = d.seq[q];
-    d.rseq[w][0] = d.rseq[w][1] = 0;
-    return SMHIP_OK;
+    return smhip::note_scratch(d, tls.op_queue, p, bytes, QueueEdge{dev});
 }
-// The library's stream handle is about to order something OUTSIDE the dispatcher (a caller's stream, a host wait, a peer
-// copy): make queue 0's tail stand for all the library's work on the device.
 void queues_join(int dev) {
     Dispatch &d = g_dispatch[dev];
     std::lock_guard<std::recursive_mutex> lock(d.m);
-    if (d.q1) (void)queue_wait(d, dev, 0, 1, d.seq[1]);
+    smhip::queues_join(d, QueueEdge{dev});
 }
-// The host has just waited for queue 0 behind a barrier: everything either queue was given is finished, so nothing on
-// record constrains the choice of queue any more.  (Without this an operator whose operands were last written long ago
-// on queue 0 would stay on queue 0 for ever: an edge to a finished operator costs nothing on the GPU, but the policy avoids
-// edges.)
 void queues_all_complete(int dev) {
     Dispatch &d = g_dispatch[dev];
     std::lock_guard<std::recursive_mutex> lock(d.m);
-    d.synced[0][1] = d.seq[1];
-    d.synced[1][0] = d.seq[0];
+    smhip::queues_all_complete(d);
 }
-// Queue 0 was just made to wait for something outside the dispatcher: queue 1's next operator orders itself behind that.
 void queues_after_external_wait(int dev) {
     Dispatch &d = g_dispatch[dev];
     std::lock_guard<std::recursive_mutex> lock(d.m);
-    d.floor[0] = ++d.seq[0];
+    smhip::queues_after_external_wait(d);
 }
 }  // namespace
 
@@ -464,9 +354,7 @@ void dispatch_single_queue(int dev, bool single) {
     if (dev < 0 || dev >= kMaxDevices) return;
     Dispatch &d = g_dispatch[dev];
     std::lock_guard<std::recursive_mutex> lock(d.m);
-    if (single && d.q1) (void)queue_wait(d, dev, 0, 1, d.seq[1]);
-    if (single) d.floor[0] = ++d.seq[0];
-    d.single = single;
+    queue_single(d, single, QueueEdge{dev});
 }
 
 int fail(int code, const char *fmt, ...) {
