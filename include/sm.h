@@ -4,3 +4,4 @@
 
 #include "UserFunctions.h"  // brings SMArray.h, the Op policies and the loop entry points with it
 #include "Sharded.h"        // sm::set_devices, sm::Sharded<T>: the same operators over the GPUs of one node
+#include "Random.h"         // sm::Generator: counter-based uniform, normal, integer and mask draws born in HBM

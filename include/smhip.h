@@ -322,6 +322,46 @@ int smhip_convert(int src_dtype, int dst_dtype, const void *a, const int64_t *st
 int smhip_convert_plan(int src_dtype, int dst_dtype, const int64_t *shape, const int64_t *strides, int ndim, int *route, int *launches,
                        int64_t *bytes_moved);
 
+/* ------------------------------------------------------------ random draws */
+/* out[i] = draw i of a counter-based generator, i = 0 .. n - 1, born in HBM (the reference has none; smhip_fill_uniform_f32 above is
+ * the benchmark's input hash and stays as it is).  Element i is a pure function of (seed, stream, offset, i) -- never of the address,
+ * the grid, the queue or the run -- so a CPU model checks the device bit for bit (tests/random_model.py) and a later call continues
+ * an earlier one: a call of n elements consumes smhip_random_blocks(kind, dtype, n) blocks, and the next call's `offset` is this
+ * one's plus that.  The generator is Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85):
+ *   key     = (low, high) 32 bits of `seed`
+ *   counter = (low 32 of b, high 32 of b, low 32 of `stream`, high 32 of `stream`),  b = offset + block index inside the call
+ * A block is four 32-bit words.  32-bit draws: element i uses word i % 4 of block i / 4.  64-bit draws: element i uses
+ * x = w[2 (i % 2)] | w[2 (i % 2) + 1] << 32 of block i / 2.
+ *   kind        dtype        draw   rule                                                                        params
+ *   BITS        i32 / i64    32/64  the word / x reinterpreted as signed                                        ignored (may be NULL)
+ *   UNIFORM     f32          32     u = (w >> 8) * 2^-24 in [0, 1);  lo + u * span, two roundings in f32,       (lo, hi)
+ *                                   span = hi - lo computed on the host in f32
+ *   UNIFORM     f64          64     u = (x >> 11) * 2^-53;  the same in f64                                     (lo, hi)
+ *   INTEGERS    i32 / i64    64     lo + mulhi64(x, R), R = hi - lo, 1 <= R <= 2^32: [lo, hi).  A value's        (lo, hi), whole numbers
+ *                                   probability is off by at most 2^-64: a relative bias of at most R / 2^64 <= 2^-32
+ *   BERNOULLI   all four     32     1 if (uint64) w < thr else 0,  thr = floor(p * 2^32) in fp64; p = 1: all ones  (p, unused)
+ *   NORMAL      f32          32     Box-Muller on the word pairs (w0, w1), (w2, w3) of block i / 4:             (mean, std)
+ *                                   u1 = ((wa >> 8) + 1) * 2^-24 in (0, 1],  t = (wb >> 8) * 2^-24,  r = sqrt(-2 log(u1)),
+ *                                   z0 = r * cospi(2t), z1 = r * sinpi(2t); elements 4b .. 4b + 3 are z0, z1 of the first pair,
+ *                                   then of the second.  mean + std * z, two roundings.  r, cospi and sinpi are each within
+ *                                   1 ULP, so z is within 5 ULP of the exact value of its formula
+ *   NORMAL      f64          64     one pair per block: u1 = ((x01 >> 11) + 1) * 2^-53, t = (x23 >> 11) * 2^-53;  (mean, std)
+ *                                   elements 2b, 2b + 1 are z0, z1
+ *   blocks consumed: ceil(n / 4) for 32-bit draws, ceil(n / 2) for 64-bit draws (INTEGERS of i32 and NORMAL of f64 included).
+ * `params` are converted to the element type on the host.  SMHIP_ERR_INVALID, with no device touched: a kind / dtype pair outside the
+ * table; non-finite params; std < 0; hi < lo (UNIFORM); bounds that are not whole numbers, lie outside the element type or have
+ * hi - lo outside 1 .. 2^32 (INTEGERS); p outside [0, 1] or NaN; offset + blocks passing 2^64; a null `out` with n > 0.  n == 0
+ * is a no-op.  `out` is dense and needs only element alignment: a slice that starts mid-vector gets the same values.  Nothing
+ * past element n - 1 is written.  Asynchronous, stream-ordered like the other operators; results of <= 4096 elements are not
+ * recorded in the tiny batch but run at once, behind everything that is recorded.  The functions themselves: csrc/sm_random.h,
+ * compiled for host and device alike. */
+typedef enum smhip_random_kind {
+    SMHIP_RANDOM_BITS = 0, SMHIP_RANDOM_UNIFORM = 1, SMHIP_RANDOM_INTEGERS = 2, SMHIP_RANDOM_BERNOULLI = 3, SMHIP_RANDOM_NORMAL = 4
+} smhip_random_kind;
+int smhip_random(int kind, int dtype, void *out, size_t n, uint64_t seed, uint64_t stream, uint64_t offset, const double params[2]);
+/* Host only, no device touched: the blocks a call of n elements consumes. */
+int smhip_random_blocks(int kind, int dtype, size_t n, uint64_t *blocks);
+
 /* ------------------------------------------------------- axis reductions */
 /* np.sum / np.mean / np.max / np.min over chosen axes (the reference reduces only whole arrays: product.h).  The contract:
  *   kind   f32                                   f64                i32 / i64

@@ -82,6 +82,8 @@ RUNS_NAN_DISTINCT = 1  # smhip_runs' flag: a NaN is a run of its own (equal_nan=
 RUNS_VALUES, RUNS_INDEX, RUNS_COUNTS, RUNS_INVERSE = 1, 2, 4, 8  # smhip_runs_plan's `outputs`
 RUNS_ROUTE_NONE, RUNS_ROUTE_ONE, RUNS_ROUTE_TILES = range(3)
 CONVERT_ROUTE_NONE, CONVERT_ROUTE_DENSE, CONVERT_ROUTE_ROWS, CONVERT_ROUTE_STAGED, CONVERT_ROUTE_COPY = range(5)  # smhip_convert_route
+RANDOM_BITS, RANDOM_UNIFORM, RANDOM_INTEGERS, RANDOM_BERNOULLI, RANDOM_NORMAL = range(5)  # smhip_random_kind
+RANDOM_KINDS = {"bits": RANDOM_BITS, "uniform": RANDOM_UNIFORM, "integers": RANDOM_INTEGERS, "bernoulli": RANDOM_BERNOULLI, "normal": RANDOM_NORMAL}
 
 ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_BROADCAST = -1, -2, -3, -4, -5
 
@@ -180,6 +182,8 @@ class Smhip:
             if name not in ("smhip_version", "smhip_last_error"):
                 fn.restype = C.c_int
         c.smhip_fill_uniform_f32.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_float, C.c_float]
+        c.smhip_random.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
+        c.smhip_random_blocks.argtypes = [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint64)]
 
     # -- plumbing ---------------------------------------------------------
     def _ck(self, rc):
@@ -424,6 +428,33 @@ class Smhip:
         self._ck(self.c.smhip_convert_plan(C.c_int(src_dtype), C.c_int(dst_dtype), arr(shape), arr(strides), C.c_int(ndim), C.byref(route),
                                            C.byref(launches), C.byref(moved)))
         return route.value, launches.value, moved.value
+
+    # -- random draws ---------------------------------------------------------------------
+    def _random_pair(self, kind, dtype, who):
+        """(kind id, dtype) of a draw; TypeError for an element type the kind is not defined for."""
+        kind = RANDOM_KINDS[kind] if isinstance(kind, str) else int(kind)
+        dt = self._convert_dtype(dtype, who)
+        floats = dt.kind == "f"
+        if (kind in (RANDOM_UNIFORM, RANDOM_NORMAL) and not floats) or (kind in (RANDOM_BITS, RANDOM_INTEGERS) and floats):
+            raise TypeError(f"{who}: not defined for element type {dt}")
+        return kind, dt
+
+    def random_blocks(self, kind, dtype, n):
+        """smhip_random_blocks (host only): the Philox blocks a call of n elements consumes."""
+        kind, dt = self._random_pair(kind, dtype, "random_blocks")
+        blocks = C.c_uint64(0)
+        self._ck(self.c.smhip_random_blocks(kind, DTYPES[dt], int(n), C.byref(blocks)))
+        return blocks.value
+
+    def random_raw(self, kind, dtype, out_ptr, n, seed, stream, offset, params):
+        """smhip_random with every argument as given (argument-validation tests); params: a pair of floats or None."""
+        pp = (C.c_double * 2)(*params) if params is not None else None
+        return self.c.smhip_random(int(kind), int(dtype), C.c_void_p(out_ptr), int(n), int(seed), int(stream), int(offset), pp)
+
+    def generator(self, seed, stream=0):
+        """A counter-based generator (sm::Generator): uniform, normal, integers, bernoulli, bits, permutation, shuffle; each call
+        advances its position by the blocks it consumed, so a program's draws are reproducible."""
+        return Generator(self, seed, stream)
 
     @staticmethod
     def _stage(st):
@@ -1532,6 +1563,71 @@ class Smhip:
 
 
 _lib = None
+
+
+class Generator:
+    """lib.generator(seed, stream=0): draws born on the device, element i a pure function of (seed, stream, offset, i) (smhip_random;
+    smhip.h has the table, tests/random_model.py the CPU model).  Every method returns a new dense DeviceArray of `shape`, or fills
+    `out` (a dense DeviceArray of the draw's dtype; `shape` is then ignored) in place; each advances `offset` by the blocks consumed.
+    A kind that is not defined for the element type raises TypeError, parameters the C ABI refuses raise ValueError."""
+
+    def __init__(self, lib, seed, stream=0):
+        self.lib, self.seed, self.stream, self.offset = lib, int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 64 - 1), 0
+
+    def seek(self, blocks):
+        self.offset = int(blocks)
+
+    def _draw(self, who, kind, shape, dtype, params, out):
+        lib = self.lib
+        if out is not None:
+            if dtype is not None and np.dtype(dtype) != out.dtype:
+                raise TypeError(f"{who}: out is {out.dtype}, the draw is {np.dtype(dtype)}")
+            dtype = out.dtype
+        kind, dt = lib._random_pair(kind, dtype, who)
+        if out is None:
+            out = lib.empty(shape, dt)
+        elif not out.is_dense():
+            raise ValueError(f"{who}: out must be dense")
+        n = out.size
+        blocks = lib.random_blocks(kind, dt, n)
+        rc = lib.random_raw(kind, DTYPES[dt], out.ptr if n else 0, n, self.seed, self.stream, self.offset, params)
+        if rc == ERR_INVALID:
+            raise ValueError(lib.c.smhip_last_error().decode())
+        lib._ck(rc)
+        self.offset += blocks
+        return out
+
+    def uniform(self, shape=None, lo=0.0, hi=1.0, dtype=None, out=None):
+        """[lo, hi): float32 (the default) or float64."""
+        return self._draw("uniform", RANDOM_UNIFORM, shape, dtype if dtype is not None or out is not None else np.float32, (float(lo), float(hi)), out)
+
+    def normal(self, shape=None, mean=0.0, std=1.0, dtype=None, out=None):
+        return self._draw("normal", RANDOM_NORMAL, shape, dtype if dtype is not None or out is not None else np.float32, (float(mean), float(std)), out)
+
+    def integers(self, lo, hi, shape=None, dtype=None, out=None):
+        """[lo, hi), 1 <= hi - lo <= 2^32: int64 (the default) or int32."""
+        lo, hi = int(lo), int(hi)
+        if int(float(lo)) != lo or int(float(hi)) != hi:
+            raise ValueError(f"integers: the bounds {lo}, {hi} are not whole numbers of a double")
+        return self._draw("integers", RANDOM_INTEGERS, shape, dtype if dtype is not None or out is not None else np.int64, (float(lo), float(hi)), out)
+
+    def bernoulli(self, p, shape=None, dtype=None, out=None):
+        """1 with probability p, else 0, in any of the four element types (float32 by default)."""
+        return self._draw("bernoulli", RANDOM_BERNOULLI, shape, dtype if dtype is not None or out is not None else np.float32, (float(p), 0.0), out)
+
+    def bits(self, shape=None, dtype=None, out=None):
+        return self._draw("bits", RANDOM_BITS, shape, dtype if dtype is not None or out is not None else np.int64, None, out)
+
+    def permutation(self, n, out=None):
+        """A random order of 0 .. n - 1 (int64): the stable argsort of n 64-bit keys."""
+        return self.lib.argsort(self.bits((int(n),), np.int64), axis=None, out=out)
+
+    def shuffle(self, a, axis=0, out=None):
+        """take(a, permutation(a.shape[axis]), axis)."""
+        axis = axis + a.ndim if axis < 0 else axis
+        if not 0 <= axis < a.ndim:
+            raise ValueError(f"shuffle: axis {axis} of an array of rank {a.ndim}")
+        return self.lib.take(a, self.permutation(a.shape[axis]), axis, mode="clip", out=out)
 
 
 def load(path: str = LIB_PATH) -> Smhip:
