@@ -31,6 +31,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "fold.hip.h"
 #include "internal.h"
@@ -371,11 +372,8 @@ int run_kind(int kind, const Plan &pl, const void *in, int64_t *idx_out, void *v
     return run_plan<T, false>(pl, static_cast<const T *>(in), idx_out, static_cast<T *>(val_out), s);
 }
 
-}  // namespace
-
 // Validation: everything that can be said without a device or a pointer.
 int argreduce_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis) {
-    using namespace axis_plan;
     if (kind != SMHIP_ARG_MAX && kind != SMHIP_ARG_MIN) return fail(SMHIP_ERR_INVALID, "%s: bad kind %d", who, kind);
     if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
     if (int rc = check_axis(who, axis, ndim)) return rc;
@@ -415,4 +413,34 @@ int launch_argreduce_axis(int kind, int dtype, const void *a, const int64_t *sha
     return fail(SMHIP_ERR_INVALID, "argreduce_axis: bad dtype %d", dtype);
 }
 
+}  // namespace
 }  // namespace smhip
+
+using namespace smhip;
+
+int smhip_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, int64_t *index_out,
+                         void *value_out) {
+    if (int rc = argreduce_axis_check("argreduce_axis", kind, dtype, shape, strides, ndim, axis)) return rc;
+    int64_t nout = 1;
+    for (int d = 0; d < ndim; ++d)
+        if (d != axis) nout *= shape[d];
+    if (nout == 0) return SMHIP_OK;
+    if (!a || !index_out) return fail(SMHIP_ERR_INVALID, "argreduce_axis: null buffer");
+    const size_t esz = dtype_size(dtype);
+    const Span sa{a, span_bytes(shape, strides, ndim, esz)}, si{index_out, (size_t)nout * sizeof(int64_t)}, sv{value_out, value_out ? (size_t)nout * esz : 0};
+    if (spans_overlap(si, sa) || spans_overlap(sv, sa) || spans_overlap(si, sv))
+        return fail(SMHIP_ERR_INVALID, "argreduce_axis: index_out / value_out overlap the operand or each other");
+    // the operand's span and the index result are declared; the call still orders itself behind everything and everything
+    // later behind it (a pooled copy, the chunks' pairs and value_out are not declared), recorded tiny operators flushed first
+    hipStream_t s;
+    OpScope op_scope_;
+    if (int rc = op_scope_.begin(&sa, 1, si, &s, true)) return rc;
+    return launch_argreduce_axis(kind, dtype, a, shape, strides, ndim, axis, index_out, value_out, s);
+}
+
+int smhip_argreduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches,
+                         int64_t *ori3, int64_t *chunk) {
+    if (int rc = argreduce_axis_check("argreduce_plan", kind, dtype, shape, strides, ndim, axis)) return rc;
+    argreduce_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
+    return SMHIP_OK;
+}

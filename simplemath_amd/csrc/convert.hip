@@ -24,6 +24,7 @@
 //   COPY    src_dtype == dst_dtype: the dense copy (the array kernel as LEFT) or the LEFT gather; no kernel of this file.
 #include <type_traits>
 
+#include "abi_args.h"
 #include "internal.h"
 #include "ops.hip.h"
 #include "sm_convert.h"
@@ -338,23 +339,17 @@ using namespace smhip;
 
 int smhip_convert(int src_dtype, int dst_dtype, const void *a, const int64_t *strides, const int64_t *shape, int ndim, void *out) {
     if (int rc = convert_check("convert", src_dtype, dst_dtype, shape, strides, ndim)) return rc;
-    int64_t n = 1, last = 0;
-    for (int i = 0; i < ndim; ++i) {
-        n *= shape[i];
-        last += (shape[i] - 1) * strides[i];
-    }
+    const int64_t n = element_count(shape, ndim);
     if (n == 0) return SMHIP_OK;
     if (!a || !out) return fail(SMHIP_ERR_INVALID, "convert: null buffer");
-    const size_t a_bytes = (size_t)(last + 1) * dtype_size(src_dtype), out_bytes = (size_t)n * dtype_size(dst_dtype);
-    const char *pa = static_cast<const char *>(a), *po = static_cast<const char *>(out);
-    if (pa < po + out_bytes && po < pa + a_bytes) return fail(SMHIP_ERR_INVALID, "convert: `out` overlaps the operand");
+    const Span read{a, span_bytes(shape, strides, ndim, dtype_size(src_dtype))}, write{out, (size_t)n * dtype_size(dst_dtype)};
+    if (spans_overlap(read, write)) return fail(SMHIP_ERR_INVALID, "convert: `out` overlaps the operand");
     const Plan pl = make_plan(src_dtype, dst_dtype, shape, strides, ndim);
     hipStream_t s;
     OpScope op_scope;
-    const Span read{a, a_bytes};
     // recorded tiny operators are flushed first; STAGED uses a pooled block that is not declared, so it orders itself behind
     // everything and everything later behind it
-    if (int rc = op_scope.begin(&read, 1, Span{out, out_bytes}, &s, pl.route == SMHIP_CONVERT_ROUTE_STAGED)) return rc;
+    if (int rc = op_scope.begin(&read, 1, write, &s, pl.route == SMHIP_CONVERT_ROUTE_STAGED)) return rc;
     return launch_convert(pl, src_dtype, dst_dtype, a, out, s);
 }
 

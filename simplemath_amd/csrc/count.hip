@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "internal.h"
 
@@ -420,8 +421,6 @@ template <typename T> int fill_edges(int64_t bins, double lo, double hi, T *edge
     return SMHIP_OK;
 }
 
-}  // namespace
-
 // Validation: everything that can be said without a device or a pointer.  *n_out: the element count of x.
 int count_check(const char *who, int what, int flags, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins) {
     if (what != SMHIP_COUNT_SEARCHSORTED && what != SMHIP_COUNT_BINCOUNT && what != SMHIP_COUNT_HISTOGRAM) return fail(SMHIP_ERR_INVALID, "%s: bad operation %d", who, what);
@@ -473,7 +472,7 @@ int histogram_edges(int dtype, int64_t bins, double lo, double hi, void *edges_h
 }
 
 // x dense over `shape`, or copied dense here.
-static int dense_operand(const Plan &p, axis_plan::Pooled *pool, int dtype, const void **x, const int64_t *shape, const int64_t *strides, int ndim, hipStream_t s) {
+int dense_operand(const Plan &p, axis_plan::Pooled *pool, int dtype, const void **x, const int64_t *shape, const int64_t *strides, int ndim, hipStream_t s) {
     if (!p.copy) return SMHIP_OK;
     return pool->dense_copy(dtype, *x, shape, strides, ndim, s, x);
 }
@@ -532,4 +531,65 @@ int launch_histogram(int flags, int dtype, const void *x, const int64_t *shape, 
     return fail(SMHIP_ERR_INVALID, "histogram: bad dtype %d", dtype);
 }
 
+}  // namespace
 }  // namespace smhip
+
+using namespace smhip;
+
+int smhip_searchsorted(int side, int dtype, const void *edges, int64_t n_edges, const void *x, const int64_t *shape, const int64_t *strides, int ndim,
+                       int64_t *out) {
+    if (side != SMHIP_SIDE_LEFT && side != SMHIP_SIDE_RIGHT) return fail(SMHIP_ERR_INVALID, "searchsorted: bad side %d", side);
+    if (int rc = count_check("searchsorted", SMHIP_COUNT_SEARCHSORTED, 0, dtype, shape, strides, ndim, n_edges)) return rc;
+    const int64_t n = element_count(shape, ndim);
+    if (n == 0) return SMHIP_OK;
+    if (!x || !out || (n_edges && !edges)) return fail(SMHIP_ERR_INVALID, "searchsorted: null operand, table or result");
+    const size_t esz = dtype_size(dtype);
+    if (misaligned(x, esz) || misaligned(edges, esz) || misaligned(out, sizeof(int64_t))) return fail(SMHIP_ERR_INVALID, "searchsorted: a pointer is not aligned to its element");
+    const Span sx{x, span_bytes(shape, strides, ndim, esz)}, se{edges, (size_t)n_edges * esz}, so{out, (size_t)n * sizeof(int64_t)};
+    if (spans_overlap(so, sx) || spans_overlap(so, se)) return fail(SMHIP_ERR_INVALID, "searchsorted: the result overlaps the operand or the table");
+    SMHIP_ACQUIRE(s);  // undeclared spans (a pooled dense copy): ordered behind everything, recorded tiny operators flushed first
+    return launch_searchsorted(side, dtype, edges, n_edges, x, shape, strides, ndim, out, s);
+}
+
+int smhip_bincount(int mode, int ids_dtype, const void *ids, const int64_t *shape, const int64_t *strides, int ndim, int64_t nbins, int64_t *counts,
+                   int64_t *bad_out) {
+    if (mode != SMHIP_INDEX_CHECKED && mode != SMHIP_INDEX_CLIP && mode != SMHIP_INDEX_WRAP) return fail(SMHIP_ERR_INVALID, "bincount: bad mode %d", mode);
+    if (int rc = count_check("bincount", SMHIP_COUNT_BINCOUNT, 0, ids_dtype, shape, strides, ndim, nbins)) return rc;
+    const int64_t n = element_count(shape, ndim);
+    if (n == 0 && nbins == 0) return SMHIP_OK;
+    if ((n && !ids) || !counts) return fail(SMHIP_ERR_INVALID, "bincount: null ids or result");
+    const size_t esz = dtype_size(ids_dtype);
+    if (misaligned(ids, esz) || misaligned(counts, sizeof(int64_t)) || misaligned(bad_out, sizeof(int64_t)))
+        return fail(SMHIP_ERR_INVALID, "bincount: a pointer is not aligned to its element");
+    const Span si{ids, n ? span_bytes(shape, strides, ndim, esz) : 0}, so{counts, (size_t)nbins * sizeof(int64_t)}, sb{bad_out, bad_out ? sizeof(int64_t) : 0};
+    if (spans_overlap(so, si) || spans_overlap(so, sb) || spans_overlap(sb, si)) return fail(SMHIP_ERR_INVALID, "bincount: the result, the ids and bad_out overlap");
+    SMHIP_ACQUIRE(s);  // undeclared spans (the pooled rows, a dense copy)
+    return launch_bincount(mode, ids_dtype, ids, shape, strides, ndim, nbins, counts, bad_out, s);
+}
+
+int smhip_histogram(int flags, int dtype, const void *x, const int64_t *shape, const int64_t *strides, int ndim, const void *edges_dev, int64_t bins, double lo,
+                    double hi, int64_t *counts) {
+    if (int rc = count_check("histogram", SMHIP_COUNT_HISTOGRAM, flags, dtype, shape, strides, ndim, bins)) return rc;
+    if (flags & SMHIP_HISTOGRAM_UNIFORM)
+        if (int rc = histogram_range_check("histogram", bins, &lo, &hi)) return rc;
+    const int64_t n = element_count(shape, ndim);
+    if (n == 0 && bins == 0) return SMHIP_OK;
+    if ((n && (!x || !edges_dev)) || !counts) return fail(SMHIP_ERR_INVALID, "histogram: null operand, table or result");
+    const size_t esz = dtype_size(dtype);
+    if (misaligned(x, esz) || misaligned(edges_dev, esz) || misaligned(counts, sizeof(int64_t))) return fail(SMHIP_ERR_INVALID, "histogram: a pointer is not aligned to its element");
+    const Span sx{x, n ? span_bytes(shape, strides, ndim, esz) : 0}, se{edges_dev, (size_t)(bins + 1) * esz}, so{counts, (size_t)bins * sizeof(int64_t)};
+    // without elements the table may be null while its length is not: its span is then still taken from address 0
+    const bool in_null_table = !edges_dev && so.bytes && reinterpret_cast<uintptr_t>(counts) < se.bytes;
+    if (spans_overlap(so, sx) || spans_overlap(so, se) || in_null_table) return fail(SMHIP_ERR_INVALID, "histogram: the result overlaps the operand or the table");
+    SMHIP_ACQUIRE(s);  // undeclared spans (the pooled rows, a dense copy)
+    return launch_histogram(flags, dtype, x, shape, strides, ndim, edges_dev, bins, lo, hi, counts, s);
+}
+
+int smhip_histogram_edges(int dtype, int64_t bins, double lo, double hi, void *edges_host) { return histogram_edges(dtype, bins, lo, hi, edges_host); }
+
+int smhip_count_plan(int what, int flags, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins, int *route, int *launches,
+                     int64_t *info6) {
+    if (int rc = count_check("count_plan", what, flags, dtype, shape, strides, ndim, bins)) return rc;
+    count_plan(what, dtype, shape, strides, ndim, bins, route, launches, info6);
+    return SMHIP_OK;
+}

@@ -227,63 +227,12 @@ int launch_cdot(const void *a, const void *b, size_t n, double *out2_dev, hipStr
 int launch_cdot32(const void *a, const void *b, size_t n, double *out2_dev, hipStream_t s);  // n {re, im} float pairs; fp64 {re, im} out
 int launch_contiguous_sum(int op, int dtype, const void *a, const void *b, void *out, size_t n, double *sum_dev,
                           hipStream_t s);
-// reduce_axis.hip: axis reductions (smhip_reduce_axes); the checks and the planner are host-only
-int reduce_axes_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask);
-void reduce_axes_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int *route, int *launches, int64_t *ori3);
-int launch_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, void *out,
-                       hipStream_t s);
-
-// scan_axis.hip: cumulative scans along an axis (smhip_scan_axis); the checks and the planner are host-only
-int scan_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis);
-void scan_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
-                    int64_t *chunk);
-int launch_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *out,
-                     hipStream_t s);
-
-// argreduce_axis.hip: argmax / argmin along an axis (smhip_argreduce_axis); the checks and the planner are host-only
-int argreduce_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis);
-void argreduce_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
-                         int64_t *chunk);
-int launch_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis,
-                          int64_t *index_out, void *value_out, hipStream_t s);
-
-// sort_axis.hip: stable sort / argsort along an axis (smhip_sort_axis); the checks and the planner are host-only
-int sort_axis_check(const char *who, int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis);
+// What the operator families export across files (each keeps its entry points, checks, planner and launcher to itself):
+// sort_axis.hip: the stable sort / argsort along an axis, which scatter_axis.hip runs on its entries' keys
 void sort_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
                     int64_t *chunk);
 int launch_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *values_out,
                      int64_t *index_out, hipStream_t s);
-
-// take_axis.hip: take / take_along_axis, the gather along an axis by int64 positions (smhip_take_axis); the checks and the planner are host-only
-int take_axis_check(const char *who, int mode, int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape,
-                    int ndim, int axis);
-void take_axis_plan(int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape, int ndim, int axis,
-                    int *route, int *launches, int64_t *oji3, int64_t *chunk);
-int launch_take_axis(int mode, int dtype, const void *a, const int64_t *a_strides, int64_t a_extent, const int64_t *idx, const int64_t *idx_strides,
-                     const int64_t *out_shape, int ndim, int axis, void *out, int64_t *bad_out, hipStream_t s);
-
-// scatter_axis.hip: put_along_axis / put / scatter_add / index_add, writing by int64 positions along an axis (smhip_scatter_axis);
-// the checks and the planner are host-only
-int scatter_axis_check(const char *who, int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides,
-                       const int64_t *val_strides, int64_t n_entries);
-void scatter_axis_plan(int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides, const int64_t *val_strides,
-                       int64_t n_entries, int *route, int *launches, int64_t *orji4, int64_t *sorted_entries);
-int launch_scatter_axis(int kind, int mode, int flags, int dtype, void *out, const int64_t *out_shape, int ndim, int axis, const int64_t *idx,
-                        const int64_t *idx_strides, const void *values, const int64_t *val_strides, int64_t n_entries, int64_t *bad_out, hipStream_t s);
-
-// count.hip: searchsorted, bincount and histogram (smhip_searchsorted / smhip_bincount / smhip_histogram); the checks, the planner and
-// the uniform edge table are host-only.  `what` is an smhip_count_op; `bins` the edges of searchsorted, the bins of the other two.
-int count_check(const char *who, int what, int flags, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins);
-void count_plan(int what, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins, int *route, int *launches, int64_t *info6);
-int histogram_range_check(const char *who, int64_t bins, double *lo, double *hi);  // numpy's refusals; a range of one point is widened by 0.5 each way
-int histogram_edges(int dtype, int64_t bins, double lo, double hi, void *edges_host);
-int launch_searchsorted(int side, int dtype, const void *edges, int64_t n_edges, const void *x, const int64_t *shape, const int64_t *strides, int ndim, int64_t *out,
-                        hipStream_t s);
-int launch_bincount(int mode, int dtype, const void *ids, const int64_t *shape, const int64_t *strides, int ndim, int64_t nbins, int64_t *counts, int64_t *bad_out,
-                    hipStream_t s);
-int launch_histogram(int flags, int dtype, const void *x, const int64_t *shape, const int64_t *strides, int ndim, const void *edges, int64_t bins, double lo, double hi,
-                     int64_t *counts, hipStream_t s);
-
 // select.hip: the exclusive prefix of per-tile counts in ONE workgroup (offsets, when given) and their sum (*total, when given), exact in
 // int64; unique.hip's compaction runs the same launch between its count and its emit.
 int launch_tile_scan(const int32_t *counts, int64_t tiles, int64_t *offsets, int64_t *total, hipStream_t s);

@@ -37,6 +37,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "fold.hip.h"
 #include "internal.h"
@@ -502,8 +503,6 @@ int run_kind(int kind, const Plan &pl, int dtype, const void *a, const int64_t *
     return fail(SMHIP_ERR_INVALID, "reduce_axes: bad kind %d", kind);
 }
 
-}  // namespace
-
 int reduce_axes_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask) {
     return check_args(who, kind, dtype, shape, strides, ndim, axes_mask);
 }
@@ -539,4 +538,24 @@ int launch_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape,
     return fail(SMHIP_ERR_INVALID, "reduce_axes: bad dtype %d", dtype);
 }
 
+}  // namespace
 }  // namespace smhip
+
+using namespace smhip;
+
+int smhip_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, void *out) {
+    if (int rc = reduce_axes_check("reduce_axes", kind, dtype, shape, strides, ndim, axes_mask)) return rc;
+    int64_t n = 1, nout = 1;
+    for (int d = 0; d < ndim; ++d) n *= shape[d], nout *= (axes_mask >> d & 1) ? 1 : shape[d];
+    if (nout == 0) return SMHIP_OK;
+    if (!out || (n && !a)) return fail(SMHIP_ERR_INVALID, "reduce_axes: null buffer");
+    SMHIP_ACQUIRE(s);  // a reduction: undeclared spans, ordered behind everything (recorded tiny operators flushed first)
+    return launch_reduce_axes(kind, dtype, a, shape, strides, ndim, axes_mask, out, s);
+}
+
+int smhip_reduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int *route, int *launches,
+                      int64_t *ori3) {
+    if (int rc = reduce_axes_check("reduce_plan", kind, dtype, shape, strides, ndim, axes_mask)) return rc;
+    reduce_axes_plan(dtype, shape, strides, ndim, axes_mask, route, launches, ori3);
+    return SMHIP_OK;
+}

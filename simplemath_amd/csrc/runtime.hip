@@ -16,6 +16,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "abi_args.h"
 #include "front_order.h"
 #include "internal.h"
 
@@ -613,23 +614,7 @@ ThreadState::~ThreadState() {
 
 using namespace smhip;
 
-// An entry point whose operand spans are not declared: a barrier operator (ordered behind everything, everything later
-// behind it) for as long as the function runs.
-#define SMHIP_ACQUIRE(stream_var)  \
-    hipStream_t stream_var;        \
-    OpScope op_scope_;             \
-    if (int rc_ = op_scope_.begin_barrier(&stream_var)) return rc_
-// An operator with declared spans: reads {ptr, bytes}..., one write.
-#define SMHIP_ACQUIRE_OP(stream_var, write_span, ...)                                                         \
-    hipStream_t stream_var;                                                                                  \
-    OpScope op_scope_;                                                                                       \
-    {                                                                                                        \
-        const Span reads_[] = {__VA_ARGS__};                                                                 \
-        if (int rc_ = op_scope_.begin(reads_, sizeof reads_ / sizeof reads_[0], write_span, &stream_var)) return rc_; \
-    }
-
 namespace {
-// Bytes from an operand's first element to its last, through `strides` over `shape`.
 // The calling thread's result slot on its current device: host pointer and the device's alias of the same 64 bytes.  A
 // synchronous reduction's kernel writes its scalar there and the host reads it after the stream has drained -- the
 // alternative (a pooled device buffer, hipMemcpyAsync device-to-host, the same wait) queued a copy packet and cost 5-8 us
@@ -652,17 +637,6 @@ int result_slot(void **host, void **dev) {
     *host = tls.result_host[d];
     *dev = tls.result_dev[d];
     return SMHIP_OK;
-}
-size_t span_bytes(const int64_t *shape, const int64_t *strides, int ndim, size_t esz) {
-    size_t last = 0;
-    for (int i = 0; i < ndim; ++i)
-        if (shape[i] > 0) last += (size_t)(shape[i] - 1) * (size_t)strides[i];
-    return (last + 1) * esz;
-}
-// Do two byte spans share a byte?  (An empty span shares none.)
-bool spans_overlap(Span x, Span y) {
-    const char *x0 = static_cast<const char *>(x.p), *y0 = static_cast<const char *>(y.p);
-    return x.bytes && y.bytes && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
 }
 }  // namespace
 
@@ -1358,219 +1332,6 @@ int smhip_contiguous_sum_async(int op, int dtype, const void *a, const void *b, 
     if (!sum_dev || (n && (!a || !b || !out))) return fail(SMHIP_ERR_INVALID, "contiguous_sum: null buffer");
     SMHIP_ACQUIRE(s);
     return launch_contiguous_sum(op, dtype, a, b, out, n, sum_dev, s);
-}
-
-int smhip_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, void *out) {
-    if (int rc = reduce_axes_check("reduce_axes", kind, dtype, shape, strides, ndim, axes_mask)) return rc;
-    int64_t n = 1, nout = 1;
-    for (int d = 0; d < ndim; ++d) n *= shape[d], nout *= (axes_mask >> d & 1) ? 1 : shape[d];
-    if (nout == 0) return SMHIP_OK;
-    if (!out || (n && !a)) return fail(SMHIP_ERR_INVALID, "reduce_axes: null buffer");
-    SMHIP_ACQUIRE(s);  // a reduction: undeclared spans, ordered behind everything (recorded tiny operators flushed first)
-    return launch_reduce_axes(kind, dtype, a, shape, strides, ndim, axes_mask, out, s);
-}
-
-int smhip_reduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int *route, int *launches,
-                      int64_t *ori3) {
-    if (int rc = reduce_axes_check("reduce_plan", kind, dtype, shape, strides, ndim, axes_mask)) return rc;
-    reduce_axes_plan(dtype, shape, strides, ndim, axes_mask, route, launches, ori3);
-    return SMHIP_OK;
-}
-
-int smhip_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *out) {
-    if (int rc = scan_axis_check("scan_axis", kind, dtype, shape, strides, ndim, axis)) return rc;
-    int64_t n = 1;
-    bool dense = true;
-    for (int d = ndim - 1; d >= 0; --d) {
-        if (shape[d] != 1 && strides[d] != n) dense = false;
-        n *= shape[d];
-    }
-    if (n == 0) return SMHIP_OK;
-    if (!a || !out) return fail(SMHIP_ERR_INVALID, "scan_axis: null buffer");
-    if (!(out == a && dense)) {  // in place is the one overlap a scan can take: a lane stores only what it has loaded itself
-        const size_t esz = dtype_size(dtype);
-        if (spans_overlap(Span{a, span_bytes(shape, strides, ndim, esz)}, Span{out, (size_t)n * esz}))
-            return fail(SMHIP_ERR_INVALID, "scan_axis: the result overlaps the operand (only out == a with a dense operand is allowed)");
-    }
-    SMHIP_ACQUIRE(s);  // undeclared spans (a pooled copy, the chunks' totals): ordered behind everything, recorded tiny operators flushed first
-    return launch_scan_axis(kind, dtype, a, shape, strides, ndim, axis, out, s);
-}
-
-int smhip_scan_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches,
-                    int64_t *ori3, int64_t *chunk) {
-    if (int rc = scan_axis_check("scan_plan", kind, dtype, shape, strides, ndim, axis)) return rc;
-    scan_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
-    return SMHIP_OK;
-}
-
-int smhip_argreduce_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, int64_t *index_out,
-                         void *value_out) {
-    if (int rc = argreduce_axis_check("argreduce_axis", kind, dtype, shape, strides, ndim, axis)) return rc;
-    int64_t nout = 1;
-    for (int d = 0; d < ndim; ++d)
-        if (d != axis) nout *= shape[d];
-    if (nout == 0) return SMHIP_OK;
-    if (!a || !index_out) return fail(SMHIP_ERR_INVALID, "argreduce_axis: null buffer");
-    const size_t esz = dtype_size(dtype);
-    const Span sa{a, span_bytes(shape, strides, ndim, esz)}, si{index_out, (size_t)nout * sizeof(int64_t)}, sv{value_out, value_out ? (size_t)nout * esz : 0};
-    if (spans_overlap(si, sa) || spans_overlap(sv, sa) || spans_overlap(si, sv))
-        return fail(SMHIP_ERR_INVALID, "argreduce_axis: index_out / value_out overlap the operand or each other");
-    // the operand's span and the index result are declared; the call still orders itself behind everything and everything
-    // later behind it (a pooled copy, the chunks' pairs and value_out are not declared), recorded tiny operators flushed first
-    hipStream_t s;
-    OpScope op_scope_;
-    if (int rc = op_scope_.begin(&sa, 1, si, &s, true)) return rc;
-    return launch_argreduce_axis(kind, dtype, a, shape, strides, ndim, axis, index_out, value_out, s);
-}
-
-int smhip_argreduce_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches,
-                         int64_t *ori3, int64_t *chunk) {
-    if (int rc = argreduce_axis_check("argreduce_plan", kind, dtype, shape, strides, ndim, axis)) return rc;
-    argreduce_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
-    return SMHIP_OK;
-}
-
-int smhip_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *values_out,
-                    int64_t *index_out) {
-    if (int rc = sort_axis_check("sort_axis", order, dtype, shape, strides, ndim, axis)) return rc;
-    int64_t n = 1;
-    bool dense = true;
-    for (int d = ndim - 1; d >= 0; --d) {
-        if (shape[d] != 1 && strides[d] != n) dense = false;
-        n *= shape[d];
-    }
-    if (n == 0) return SMHIP_OK;
-    if (!a) return fail(SMHIP_ERR_INVALID, "sort_axis: null operand");
-    if (!values_out && !index_out) return fail(SMHIP_ERR_INVALID, "sort_axis: neither values_out nor index_out is given");
-    const size_t esz = dtype_size(dtype);
-    const Span sa{a, span_bytes(shape, strides, ndim, esz)}, sv{values_out, values_out ? (size_t)n * esz : 0},
-        si{index_out, index_out ? (size_t)n * sizeof(int64_t) : 0};
-    // in place is the one overlap a sort can take: the operand is read whole (a line, or launch 1 of a merge) before a result is written
-    if (!(values_out == a && dense) && spans_overlap(sv, sa))
-        return fail(SMHIP_ERR_INVALID, "sort_axis: values_out overlaps the operand (only values_out == a with a dense operand is allowed)");
-    if (spans_overlap(si, sa) || spans_overlap(si, sv)) return fail(SMHIP_ERR_INVALID, "sort_axis: index_out overlaps the operand or values_out");
-    SMHIP_ACQUIRE(s);  // undeclared spans (pooled staging, the merge's pairs): ordered behind everything, recorded tiny operators flushed first
-    return launch_sort_axis(order, dtype, a, shape, strides, ndim, axis, values_out, index_out, s);
-}
-
-int smhip_sort_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
-                    int64_t *chunk) {
-    if (int rc = sort_axis_check("sort_plan", order, dtype, shape, strides, ndim, axis)) return rc;
-    sort_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
-    return SMHIP_OK;
-}
-
-int smhip_take_axis(int mode, int dtype, const void *a, const int64_t *a_strides, int64_t a_extent, const int64_t *idx, const int64_t *idx_strides,
-                    const int64_t *out_shape, int ndim, int axis, void *out, int64_t *bad_out) {
-    if (int rc = take_axis_check("take_axis", mode, dtype, a_strides, a_extent, idx_strides, out_shape, ndim, axis)) return rc;
-    int64_t n = 1, shape_a[SMHIP_MAX_NDIM];
-    for (int d = 0; d < ndim; ++d) n *= out_shape[d], shape_a[d] = d == axis ? a_extent : out_shape[d];
-    if (n == 0) return SMHIP_OK;
-    if (!a || !idx || !out) return fail(SMHIP_ERR_INVALID, "take_axis: null operand, index array or result");
-    const size_t esz = dtype_size(dtype);
-    const Span sa{a, span_bytes(shape_a, a_strides, ndim, esz)}, si{idx, span_bytes(out_shape, idx_strides, ndim, sizeof(int64_t))},
-        so{out, (size_t)n * esz}, sb{bad_out, bad_out ? sizeof(int64_t) : 0};
-    if (spans_overlap(so, sa) || spans_overlap(so, si) || spans_overlap(so, sb))
-        return fail(SMHIP_ERR_INVALID, "take_axis: the result overlaps the operand, the index array or bad_out");
-    if (spans_overlap(sb, sa) || spans_overlap(sb, si)) return fail(SMHIP_ERR_INVALID, "take_axis: bad_out overlaps the operand or the index array");
-    SMHIP_ACQUIRE(s);  // undeclared spans (pooled dense copies): ordered behind everything, recorded tiny operators flushed first
-    return launch_take_axis(mode, dtype, a, a_strides, a_extent, idx, idx_strides, out_shape, ndim, axis, out, bad_out, s);
-}
-
-int smhip_take_plan(int mode, int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape, int ndim, int axis,
-                    int *route, int *launches, int64_t *oji3, int64_t *chunk) {
-    if (int rc = take_axis_check("take_plan", mode, dtype, a_strides, a_extent, idx_strides, out_shape, ndim, axis)) return rc;
-    take_axis_plan(dtype, a_strides, a_extent, idx_strides, out_shape, ndim, axis, route, launches, oji3, chunk);
-    return SMHIP_OK;
-}
-
-int smhip_scatter_axis(int kind, int mode, int flags, int dtype, void *out, const int64_t *out_shape, int ndim, int axis, const int64_t *idx,
-                       const int64_t *idx_strides, const void *values, const int64_t *val_strides, int64_t n_entries, int64_t *bad_out) {
-    if (int rc = scatter_axis_check("scatter_axis", kind, mode, flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries)) return rc;
-    int64_t n = 1, n_out = 1, walk_shape[SMHIP_MAX_NDIM];
-    for (int d = 0; d < ndim; ++d) walk_shape[d] = d == axis ? n_entries : out_shape[d], n *= walk_shape[d], n_out *= out_shape[d];
-    if (n == 0) return SMHIP_OK;
-    if (!out || !idx || !values) return fail(SMHIP_ERR_INVALID, "scatter_axis: null target, index array or values");
-    const size_t esz = dtype_size(dtype);
-    const Span so{out, (size_t)n_out * esz}, si{idx, span_bytes(walk_shape, idx_strides, ndim, sizeof(int64_t))},
-        sv{values, span_bytes(walk_shape, val_strides, ndim, esz)}, sb{bad_out, bad_out ? sizeof(int64_t) : 0};
-    if (spans_overlap(so, si) || spans_overlap(so, sv) || spans_overlap(so, sb))
-        return fail(SMHIP_ERR_INVALID, "scatter_axis: the target overlaps the index array, the values or bad_out");
-    if (spans_overlap(sb, si) || spans_overlap(sb, sv)) return fail(SMHIP_ERR_INVALID, "scatter_axis: bad_out overlaps the index array or the values");
-    SMHIP_ACQUIRE(s);  // undeclared spans (pooled copies, the sorted lists): ordered behind everything, recorded tiny operators flushed first
-    return launch_scatter_axis(kind, mode, flags, dtype, out, out_shape, ndim, axis, idx, idx_strides, values, val_strides, n_entries, bad_out, s);
-}
-
-int smhip_scatter_plan(int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides,
-                       const int64_t *val_strides, int64_t n_entries, int *route, int *launches, int64_t *orji4, int64_t *sorted_entries) {
-    if (int rc = scatter_axis_check("scatter_plan", kind, mode, flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries)) return rc;
-    scatter_axis_plan(flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries, route, launches, orji4, sorted_entries);
-    return SMHIP_OK;
-}
-
-namespace {
-int64_t count_of(const int64_t *shape, int ndim) {
-    int64_t n = 1;
-    for (int d = 0; d < ndim; ++d) n *= shape[d];
-    return n;
-}
-bool misaligned(const void *p, size_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) != 0; }
-}  // namespace
-
-int smhip_searchsorted(int side, int dtype, const void *edges, int64_t n_edges, const void *x, const int64_t *shape, const int64_t *strides, int ndim,
-                       int64_t *out) {
-    if (side != SMHIP_SIDE_LEFT && side != SMHIP_SIDE_RIGHT) return fail(SMHIP_ERR_INVALID, "searchsorted: bad side %d", side);
-    if (int rc = count_check("searchsorted", SMHIP_COUNT_SEARCHSORTED, 0, dtype, shape, strides, ndim, n_edges)) return rc;
-    const int64_t n = count_of(shape, ndim);
-    if (n == 0) return SMHIP_OK;
-    if (!x || !out || (n_edges && !edges)) return fail(SMHIP_ERR_INVALID, "searchsorted: null operand, table or result");
-    const size_t esz = dtype_size(dtype);
-    if (misaligned(x, esz) || misaligned(edges, esz) || misaligned(out, sizeof(int64_t))) return fail(SMHIP_ERR_INVALID, "searchsorted: a pointer is not aligned to its element");
-    const Span sx{x, span_bytes(shape, strides, ndim, esz)}, se{edges, (size_t)n_edges * esz}, so{out, (size_t)n * sizeof(int64_t)};
-    if (spans_overlap(so, sx) || spans_overlap(so, se)) return fail(SMHIP_ERR_INVALID, "searchsorted: the result overlaps the operand or the table");
-    SMHIP_ACQUIRE(s);  // undeclared spans (a pooled dense copy): ordered behind everything, recorded tiny operators flushed first
-    return launch_searchsorted(side, dtype, edges, n_edges, x, shape, strides, ndim, out, s);
-}
-
-int smhip_bincount(int mode, int ids_dtype, const void *ids, const int64_t *shape, const int64_t *strides, int ndim, int64_t nbins, int64_t *counts,
-                   int64_t *bad_out) {
-    if (mode != SMHIP_INDEX_CHECKED && mode != SMHIP_INDEX_CLIP && mode != SMHIP_INDEX_WRAP) return fail(SMHIP_ERR_INVALID, "bincount: bad mode %d", mode);
-    if (int rc = count_check("bincount", SMHIP_COUNT_BINCOUNT, 0, ids_dtype, shape, strides, ndim, nbins)) return rc;
-    const int64_t n = count_of(shape, ndim);
-    if (n == 0 && nbins == 0) return SMHIP_OK;
-    if ((n && !ids) || !counts) return fail(SMHIP_ERR_INVALID, "bincount: null ids or result");
-    const size_t esz = dtype_size(ids_dtype);
-    if (misaligned(ids, esz) || misaligned(counts, sizeof(int64_t)) || misaligned(bad_out, sizeof(int64_t)))
-        return fail(SMHIP_ERR_INVALID, "bincount: a pointer is not aligned to its element");
-    const Span si{ids, n ? span_bytes(shape, strides, ndim, esz) : 0}, so{counts, (size_t)nbins * sizeof(int64_t)}, sb{bad_out, bad_out ? sizeof(int64_t) : 0};
-    if (spans_overlap(so, si) || spans_overlap(so, sb) || spans_overlap(sb, si)) return fail(SMHIP_ERR_INVALID, "bincount: the result, the ids and bad_out overlap");
-    SMHIP_ACQUIRE(s);  // undeclared spans (the pooled rows, a dense copy)
-    return launch_bincount(mode, ids_dtype, ids, shape, strides, ndim, nbins, counts, bad_out, s);
-}
-
-int smhip_histogram(int flags, int dtype, const void *x, const int64_t *shape, const int64_t *strides, int ndim, const void *edges_dev, int64_t bins, double lo,
-                    double hi, int64_t *counts) {
-    if (int rc = count_check("histogram", SMHIP_COUNT_HISTOGRAM, flags, dtype, shape, strides, ndim, bins)) return rc;
-    if (flags & SMHIP_HISTOGRAM_UNIFORM)
-        if (int rc = histogram_range_check("histogram", bins, &lo, &hi)) return rc;
-    const int64_t n = count_of(shape, ndim);
-    if (n == 0 && bins == 0) return SMHIP_OK;
-    if ((n && (!x || !edges_dev)) || !counts) return fail(SMHIP_ERR_INVALID, "histogram: null operand, table or result");
-    const size_t esz = dtype_size(dtype);
-    if (misaligned(x, esz) || misaligned(edges_dev, esz) || misaligned(counts, sizeof(int64_t))) return fail(SMHIP_ERR_INVALID, "histogram: a pointer is not aligned to its element");
-    const Span sx{x, n ? span_bytes(shape, strides, ndim, esz) : 0}, se{edges_dev, (size_t)(bins + 1) * esz}, so{counts, (size_t)bins * sizeof(int64_t)};
-    if (spans_overlap(so, sx) || spans_overlap(so, se)) return fail(SMHIP_ERR_INVALID, "histogram: the result overlaps the operand or the table");
-    SMHIP_ACQUIRE(s);  // undeclared spans (the pooled rows, a dense copy)
-    return launch_histogram(flags, dtype, x, shape, strides, ndim, edges_dev, bins, lo, hi, counts, s);
-}
-
-int smhip_histogram_edges(int dtype, int64_t bins, double lo, double hi, void *edges_host) { return histogram_edges(dtype, bins, lo, hi, edges_host); }
-
-int smhip_count_plan(int what, int flags, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int64_t bins, int *route, int *launches,
-                     int64_t *info6) {
-    if (int rc = count_check("count_plan", what, flags, dtype, shape, strides, ndim, bins)) return rc;
-    count_plan(what, dtype, shape, strides, ndim, bins, route, launches, info6);
-    return SMHIP_OK;
 }
 
 int smhip_sum(int dtype, const void *a, size_t n, double *out_host) {

@@ -34,6 +34,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "fold.hip.h"
 #include "internal.h"
@@ -439,11 +440,8 @@ int run_kind(int kind, const Plan &pl, const void *in, void *out, hipStream_t s)
     return fail(SMHIP_ERR_INVALID, "scan_axis: bad kind %d", kind);
 }
 
-}  // namespace
-
 // Validation: everything that can be said without a device.
 int scan_axis_check(const char *who, int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis) {
-    using namespace axis_plan;
     if (kind < SMHIP_SCAN_SUM || kind > SMHIP_SCAN_MIN) return fail(SMHIP_ERR_INVALID, "%s: bad kind %d", who, kind);
     if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
     if (int rc = check_axis(who, axis, ndim)) return rc;
@@ -483,4 +481,29 @@ int launch_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, c
     return fail(SMHIP_ERR_INVALID, "scan_axis: bad dtype %d", dtype);
 }
 
+}  // namespace
 }  // namespace smhip
+
+using namespace smhip;
+
+int smhip_scan_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *out) {
+    if (int rc = scan_axis_check("scan_axis", kind, dtype, shape, strides, ndim, axis)) return rc;
+    const int64_t n = element_count(shape, ndim);
+    const bool dense = axis_plan::row_major(shape, strides, ndim);
+    if (n == 0) return SMHIP_OK;
+    if (!a || !out) return fail(SMHIP_ERR_INVALID, "scan_axis: null buffer");
+    if (!(out == a && dense)) {  // in place is the one overlap a scan can take: a lane stores only what it has loaded itself
+        const size_t esz = dtype_size(dtype);
+        if (spans_overlap(Span{a, span_bytes(shape, strides, ndim, esz)}, Span{out, (size_t)n * esz}))
+            return fail(SMHIP_ERR_INVALID, "scan_axis: the result overlaps the operand (only out == a with a dense operand is allowed)");
+    }
+    SMHIP_ACQUIRE(s);  // undeclared spans (a pooled copy, the chunks' totals): ordered behind everything, recorded tiny operators flushed first
+    return launch_scan_axis(kind, dtype, a, shape, strides, ndim, axis, out, s);
+}
+
+int smhip_scan_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches,
+                    int64_t *ori3, int64_t *chunk) {
+    if (int rc = scan_axis_check("scan_plan", kind, dtype, shape, strides, ndim, axis)) return rc;
+    scan_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
+    return SMHIP_OK;
+}

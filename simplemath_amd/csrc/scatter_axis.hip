@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "internal.h"
 
@@ -437,12 +438,9 @@ int run_plan(const Plan &p, int mode, void *out, const int64_t *idx, const void 
     return fail(SMHIP_ERR_INVALID, "scatter_axis: bad mode %d", mode);
 }
 
-}  // namespace
-
 // Validation: everything that can be said without a device or a pointer.
 int scatter_axis_check(const char *who, int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides,
                        const int64_t *val_strides, int64_t n_entries) {
-    using namespace axis_plan;
     if (kind != SMHIP_SCATTER_PUT && kind != SMHIP_SCATTER_ADD) return fail(SMHIP_ERR_INVALID, "%s: bad kind %d", who, kind);
     if (mode != SMHIP_INDEX_CHECKED && mode != SMHIP_INDEX_CLIP && mode != SMHIP_INDEX_WRAP) return fail(SMHIP_ERR_INVALID, "%s: bad mode %d", who, mode);
     if (flags & ~SMHIP_SCATTER_UNIQUE) return fail(SMHIP_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
@@ -483,7 +481,6 @@ void scatter_axis_plan(int flags, int dtype, const int64_t *out_shape, int ndim,
 
 int launch_scatter_axis(int kind, int mode, int flags, int dtype, void *out, const int64_t *out_shape, int ndim, int axis, const int64_t *idx,
                         const int64_t *idx_strides, const void *values, const int64_t *val_strides, int64_t n_entries, int64_t *bad_out, hipStream_t s) {
-    using namespace axis_plan;
     Plan pl;
     make_plan(flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries, &pl);
     if (pl.route == SMHIP_SCATTER_ROUTE_NONE) return SMHIP_OK;
@@ -508,4 +505,31 @@ int launch_scatter_axis(int kind, int mode, int flags, int dtype, void *out, con
     return fail(SMHIP_ERR_INVALID, "scatter_axis: bad dtype %d", dtype);
 }
 
+}  // namespace
 }  // namespace smhip
+
+using namespace smhip;
+
+int smhip_scatter_axis(int kind, int mode, int flags, int dtype, void *out, const int64_t *out_shape, int ndim, int axis, const int64_t *idx,
+                       const int64_t *idx_strides, const void *values, const int64_t *val_strides, int64_t n_entries, int64_t *bad_out) {
+    if (int rc = scatter_axis_check("scatter_axis", kind, mode, flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries)) return rc;
+    int64_t n = 1, n_out = 1, walk_shape[SMHIP_MAX_NDIM];
+    for (int d = 0; d < ndim; ++d) walk_shape[d] = d == axis ? n_entries : out_shape[d], n *= walk_shape[d], n_out *= out_shape[d];
+    if (n == 0) return SMHIP_OK;
+    if (!out || !idx || !values) return fail(SMHIP_ERR_INVALID, "scatter_axis: null target, index array or values");
+    const size_t esz = dtype_size(dtype);
+    const Span so{out, (size_t)n_out * esz}, si{idx, span_bytes(walk_shape, idx_strides, ndim, sizeof(int64_t))},
+        sv{values, span_bytes(walk_shape, val_strides, ndim, esz)}, sb{bad_out, bad_out ? sizeof(int64_t) : 0};
+    if (spans_overlap(so, si) || spans_overlap(so, sv) || spans_overlap(so, sb))
+        return fail(SMHIP_ERR_INVALID, "scatter_axis: the target overlaps the index array, the values or bad_out");
+    if (spans_overlap(sb, si) || spans_overlap(sb, sv)) return fail(SMHIP_ERR_INVALID, "scatter_axis: bad_out overlaps the index array or the values");
+    SMHIP_ACQUIRE(s);  // undeclared spans (pooled copies, the sorted lists): ordered behind everything, recorded tiny operators flushed first
+    return launch_scatter_axis(kind, mode, flags, dtype, out, out_shape, ndim, axis, idx, idx_strides, values, val_strides, n_entries, bad_out, s);
+}
+
+int smhip_scatter_plan(int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides,
+                       const int64_t *val_strides, int64_t n_entries, int *route, int *launches, int64_t *orji4, int64_t *sorted_entries) {
+    if (int rc = scatter_axis_check("scatter_plan", kind, mode, flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries)) return rc;
+    scatter_axis_plan(flags, dtype, out_shape, ndim, axis, idx_strides, val_strides, n_entries, route, launches, orji4, sorted_entries);
+    return SMHIP_OK;
+}

@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "internal.h"
 #include "ops.hip.h"
@@ -431,18 +432,6 @@ template <typename T> int run_select(int what, int src_bytes, const Plan &p, Sel
     return launch(what, kModeEmit, blocks);
 }
 
-size_t view_span_bytes(const int64_t *shape, const int64_t *strides, int ndim, size_t esz) {
-    size_t last = 0;
-    for (int d = 0; d < ndim; ++d)
-        if (shape[d] > 0) last += (size_t)(shape[d] - 1) * (size_t)strides[d];
-    return (last + 1) * esz;
-}
-bool overlap(Span x, Span y) {
-    const char *x0 = static_cast<const char *>(x.p), *y0 = static_cast<const char *>(y.p);
-    return x.bytes && y.bytes && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
-}
-bool misaligned(const void *p, size_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) != 0; }
-
 // Everything that can be said about a condition's shape without a device or a pointer; *n_out = the element count.
 int check_view(const char *who, const char *name, const int64_t *shape, const int64_t *strides, int ndim, bool empty) {
     if (!strides) return fail(SMHIP_ERR_INVALID, "%s: null strides of %s", who, name);
@@ -552,8 +541,8 @@ int smhip_where(int cmp, int dtype, const void *x, const int64_t *x_strides, con
     const Span so{out, (size_t)n * esz};
     Span reads[4];
     for (int k = 0; k < 4; ++k) {
-        reads[k] = ptr[k] ? Span{ptr[k], view_span_bytes(shape, st[k], ndim, esz)} : Span{nullptr, 0};
-        if (!ptr[k] || !overlap(reads[k], so)) continue;
+        reads[k] = ptr[k] ? Span{ptr[k], span_bytes(shape, st[k], ndim, esz)} : Span{nullptr, 0};
+        if (!ptr[k] || !spans_overlap(reads[k], so)) continue;
         if (!(ptr[k] == out && row_major(shape, st[k], ndim)))
             return fail(SMHIP_ERR_INVALID, "where: the result overlaps operand %s (only out == an operand that is dense over the result's shape is allowed)", name[k]);
     }
@@ -607,8 +596,8 @@ int smhip_select_count(int cmp, int dtype, const void *x, const int64_t *x_strid
     if (n && !y && cmp != SMHIP_CMP_NONZERO && !rhs_scalar_host) return fail(SMHIP_ERR_INVALID, "select_count: the right-hand side is a scalar but its host pointer is null");
     const size_t esz = dtype_size(dtype);
     if (misaligned(x, esz) || misaligned(y, esz) || misaligned(count_dev, sizeof(int64_t))) return fail(SMHIP_ERR_INVALID, "select_count: a pointer is not aligned to its element");
-    const Span sx{x, n ? view_span_bytes(shape, x_strides, ndim, esz) : 0}, sy{y, n && y ? view_span_bytes(shape, y_strides, ndim, esz) : 0}, sc{count_dev, sizeof(int64_t)};
-    if (overlap(sc, sx) || overlap(sc, sy)) return fail(SMHIP_ERR_INVALID, "select_count: the result overlaps an operand");
+    const Span sx{x, n ? span_bytes(shape, x_strides, ndim, esz) : 0}, sy{y, n && y ? span_bytes(shape, y_strides, ndim, esz) : 0}, sc{count_dev, sizeof(int64_t)};
+    if (spans_overlap(sc, sx) || spans_overlap(sc, sy)) return fail(SMHIP_ERR_INVALID, "select_count: the result overlaps an operand");
     hipStream_t s;
     OpScope op_scope;  // undeclared spans (the pooled counts, a dense copy): ordered behind everything, recorded tiny operators flushed first
     if (int rc = op_scope.begin_barrier(&s)) return rc;
@@ -642,11 +631,14 @@ int smhip_select(int what, int cmp, int dtype, const void *x, const int64_t *x_s
     if (n && !y && cmp != SMHIP_CMP_NONZERO && !rhs_scalar_host) return fail(SMHIP_ERR_INVALID, "select: the right-hand side is a scalar but its host pointer is null");
     if (misaligned(x, esz) || misaligned(y, esz) || (values && misaligned(src, item)) || misaligned(out, item))
         return fail(SMHIP_ERR_INVALID, "select: a pointer is not aligned to its element");
-    const Span sx{x, n ? view_span_bytes(shape, x_strides, ndim, esz) : 0}, sy{y, n && y ? view_span_bytes(shape, y_strides, ndim, esz) : 0},
-        ss{src, n && values && src ? view_span_bytes(shape, src_strides, ndim, item) : 0},
+    const Span sx{x, n ? span_bytes(shape, x_strides, ndim, esz) : 0}, sy{y, n && y ? span_bytes(shape, y_strides, ndim, esz) : 0},
+        ss{src, n && values && src ? span_bytes(shape, src_strides, ndim, item) : 0},
         so{out, (size_t)capacity * item * (what == SMHIP_SELECT_COORDS ? (size_t)ndim : 1)}, sc{count_dev, count_dev ? sizeof(int64_t) : 0};
-    if (overlap(so, sx) || overlap(so, sy) || overlap(so, ss)) return fail(SMHIP_ERR_INVALID, "select: the result overlaps an operand");
-    if (overlap(sc, sx) || overlap(sc, sy) || overlap(sc, ss) || overlap(sc, so)) return fail(SMHIP_ERR_INVALID, "select: count_dev overlaps an operand or the result");
+    if (spans_overlap(so, sx) || spans_overlap(so, sy) || spans_overlap(so, ss)) return fail(SMHIP_ERR_INVALID, "select: the result overlaps an operand");
+    // with nothing to select from the result may be null while its capacity is not: its span is then still taken from address 0
+    const bool in_null_result = !out && sc.bytes && reinterpret_cast<uintptr_t>(count_dev) < so.bytes;
+    if (spans_overlap(sc, sx) || spans_overlap(sc, sy) || spans_overlap(sc, ss) || spans_overlap(sc, so) || in_null_result)
+        return fail(SMHIP_ERR_INVALID, "select: count_dev overlaps an operand or the result");
     if ((n == 0 || capacity == 0) && !count_dev) return SMHIP_OK;
     hipStream_t s;
     OpScope op_scope;  // undeclared spans (the pooled counts, dense copies): ordered behind everything, recorded tiny operators flushed first

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "internal.h"
 
@@ -299,11 +300,8 @@ int run_plan(const Plan &p, int desc, int dtype, const void *a, const int64_t *s
     return SMHIP_OK;
 }
 
-}  // namespace
-
 // Validation: everything that can be said without a device or a pointer.
 int sort_axis_check(const char *who, int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis) {
-    using namespace axis_plan;
     if (order != SMHIP_SORT_ASCENDING && order != SMHIP_SORT_DESCENDING) return fail(SMHIP_ERR_INVALID, "%s: bad order %d", who, order);
     if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
     if (int rc = check_axis(who, axis, ndim)) return rc;
@@ -311,6 +309,8 @@ int sort_axis_check(const char *who, int order, int dtype, const int64_t *shape,
     if (shape[axis] >= kMaxAxis) return fail(SMHIP_ERR_UNSUPPORTED, "%s: an axis of %lld elements (positions are 32 bits wide: below 2^31)", who, (long long)shape[axis]);
     return SMHIP_OK;
 }
+
+}  // namespace
 
 void sort_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3, int64_t *chunk) {
     (void)dtype;  // K is the same for 4- and 8-byte elements
@@ -346,3 +346,31 @@ int launch_sort_axis(int order, int dtype, const void *a, const int64_t *shape, 
 }
 
 }  // namespace smhip
+
+using namespace smhip;
+
+int smhip_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *values_out,
+                    int64_t *index_out) {
+    if (int rc = sort_axis_check("sort_axis", order, dtype, shape, strides, ndim, axis)) return rc;
+    const int64_t n = element_count(shape, ndim);
+    const bool dense = axis_plan::row_major(shape, strides, ndim);
+    if (n == 0) return SMHIP_OK;
+    if (!a) return fail(SMHIP_ERR_INVALID, "sort_axis: null operand");
+    if (!values_out && !index_out) return fail(SMHIP_ERR_INVALID, "sort_axis: neither values_out nor index_out is given");
+    const size_t esz = dtype_size(dtype);
+    const Span sa{a, span_bytes(shape, strides, ndim, esz)}, sv{values_out, values_out ? (size_t)n * esz : 0},
+        si{index_out, index_out ? (size_t)n * sizeof(int64_t) : 0};
+    // in place is the one overlap a sort can take: the operand is read whole (a line, or launch 1 of a merge) before a result is written
+    if (!(values_out == a && dense) && spans_overlap(sv, sa))
+        return fail(SMHIP_ERR_INVALID, "sort_axis: values_out overlaps the operand (only values_out == a with a dense operand is allowed)");
+    if (spans_overlap(si, sa) || spans_overlap(si, sv)) return fail(SMHIP_ERR_INVALID, "sort_axis: index_out overlaps the operand or values_out");
+    SMHIP_ACQUIRE(s);  // undeclared spans (pooled staging, the merge's pairs): ordered behind everything, recorded tiny operators flushed first
+    return launch_sort_axis(order, dtype, a, shape, strides, ndim, axis, values_out, index_out, s);
+}
+
+int smhip_sort_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int *route, int *launches, int64_t *ori3,
+                    int64_t *chunk) {
+    if (int rc = sort_axis_check("sort_plan", order, dtype, shape, strides, ndim, axis)) return rc;
+    sort_axis_plan(dtype, shape, strides, ndim, axis, route, launches, ori3, chunk);
+    return SMHIP_OK;
+}

@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "internal.h"
 
@@ -332,12 +333,9 @@ int run_plan(const Plan &p, int mode, const void *a, const int64_t *idx, void *o
     return fail(SMHIP_ERR_INVALID, "take_axis: bad mode %d", mode);
 }
 
-}  // namespace
-
 // Validation: everything that can be said without a device or a pointer.
 int take_axis_check(const char *who, int mode, int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape,
                     int ndim, int axis) {
-    using namespace axis_plan;
     if (mode != SMHIP_INDEX_CHECKED && mode != SMHIP_INDEX_CLIP && mode != SMHIP_INDEX_WRAP) return fail(SMHIP_ERR_INVALID, "%s: bad mode %d", who, mode);
     if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
     if (int rc = check_axis(who, axis, ndim)) return rc;
@@ -375,7 +373,6 @@ void take_axis_plan(int dtype, const int64_t *a_strides, int64_t a_extent, const
 
 int launch_take_axis(int mode, int dtype, const void *a, const int64_t *a_strides, int64_t a_extent, const int64_t *idx, const int64_t *idx_strides,
                      const int64_t *out_shape, int ndim, int axis, void *out, int64_t *bad_out, hipStream_t s) {
-    using namespace axis_plan;
     Plan pl;
     make_plan(dtype, a_strides, a_extent, idx_strides, out_shape, ndim, axis, &pl);
     if (pl.route == SMHIP_TAKE_ROUTE_NONE) return SMHIP_OK;
@@ -394,4 +391,31 @@ int launch_take_axis(int mode, int dtype, const void *a, const int64_t *a_stride
     return dtype_size(dtype) == 4 ? run_plan<uint32_t>(pl, mode, a, idx, out, bad_out, s) : run_plan<uint64_t>(pl, mode, a, idx, out, bad_out, s);
 }
 
+}  // namespace
 }  // namespace smhip
+
+using namespace smhip;
+
+int smhip_take_axis(int mode, int dtype, const void *a, const int64_t *a_strides, int64_t a_extent, const int64_t *idx, const int64_t *idx_strides,
+                    const int64_t *out_shape, int ndim, int axis, void *out, int64_t *bad_out) {
+    if (int rc = take_axis_check("take_axis", mode, dtype, a_strides, a_extent, idx_strides, out_shape, ndim, axis)) return rc;
+    int64_t n = 1, shape_a[SMHIP_MAX_NDIM];
+    for (int d = 0; d < ndim; ++d) n *= out_shape[d], shape_a[d] = d == axis ? a_extent : out_shape[d];
+    if (n == 0) return SMHIP_OK;
+    if (!a || !idx || !out) return fail(SMHIP_ERR_INVALID, "take_axis: null operand, index array or result");
+    const size_t esz = dtype_size(dtype);
+    const Span sa{a, span_bytes(shape_a, a_strides, ndim, esz)}, si{idx, span_bytes(out_shape, idx_strides, ndim, sizeof(int64_t))},
+        so{out, (size_t)n * esz}, sb{bad_out, bad_out ? sizeof(int64_t) : 0};
+    if (spans_overlap(so, sa) || spans_overlap(so, si) || spans_overlap(so, sb))
+        return fail(SMHIP_ERR_INVALID, "take_axis: the result overlaps the operand, the index array or bad_out");
+    if (spans_overlap(sb, sa) || spans_overlap(sb, si)) return fail(SMHIP_ERR_INVALID, "take_axis: bad_out overlaps the operand or the index array");
+    SMHIP_ACQUIRE(s);  // undeclared spans (pooled dense copies): ordered behind everything, recorded tiny operators flushed first
+    return launch_take_axis(mode, dtype, a, a_strides, a_extent, idx, idx_strides, out_shape, ndim, axis, out, bad_out, s);
+}
+
+int smhip_take_plan(int mode, int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape, int ndim, int axis,
+                    int *route, int *launches, int64_t *oji3, int64_t *chunk) {
+    if (int rc = take_axis_check("take_plan", mode, dtype, a_strides, a_extent, idx_strides, out_shape, ndim, axis)) return rc;
+    take_axis_plan(dtype, a_strides, a_extent, idx_strides, out_shape, ndim, axis, route, launches, oji3, chunk);
+    return SMHIP_OK;
+}

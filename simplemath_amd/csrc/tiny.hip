@@ -29,6 +29,7 @@
 #include <mutex>
 #include <vector>
 
+#include "abi_args.h"
 #include "internal.h"
 #include "ops.hip.h"
 
@@ -179,12 +180,6 @@ struct TinyQueue {
 TinyQueue g_tiny[kTinyDevices];
 std::atomic<int> g_tiny_pending{0};
 
-bool overlap(const Span &x, const Span &y) {
-    if (!x.p || !y.p || !x.bytes || !y.bytes) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(x.p), b = reinterpret_cast<uintptr_t>(y.p);
-    return a < b + y.bytes && b < a + x.bytes;
-}
-
 // The recorded block in launch order: list heads first, one descriptor slot each, then everything else (TinyArgs).
 template <int BYTES>
 void lay_out(const TinyQueue &q, TinyArgs<BYTES> &args) {
@@ -277,8 +272,8 @@ bool tiny_defer_free(int dev, void *p, size_t bytes) {
     if (q.count == 0 || q.flushing) return false;
     const Span blk{p, bytes};
     bool used = false;
-    for (int i = 0; i < q.count && !used; ++i) used = overlap(blk, q.writes[i]);
-    for (int i = 0; i < q.n_reads && !used; ++i) used = overlap(blk, q.reads[i]);
+    for (int i = 0; i < q.count && !used; ++i) used = spans_overlap(blk, q.writes[i]);
+    for (int i = 0; i < q.n_reads && !used; ++i) used = spans_overlap(blk, q.reads[i]);
     if (!used) return false;
     q.deferred.push_back(p);
     return true;
@@ -318,7 +313,7 @@ int tiny_try_enqueue(int op, int dtype, const void *a, size_t a_host_bytes, cons
     const Span w{out, kind == 2 ? (size_t)(span_b + 1) * esz : (size_t)n * esz};
     const Span ra{(a_host_bytes || kind == 1) ? nullptr : a, (a_host_bytes || kind == 1) ? 0 : (size_t)(span_a + 1) * esz};
     const Span rb{(b_host_bytes || scalar_host || kind != 0) ? nullptr : b, (b_host_bytes || scalar_host || kind != 0) ? 0 : (size_t)(span_b + 1) * esz};
-    if (overlap(w, ra) || overlap(w, rb)) return SMHIP_OK;  // in place: the one-launch path has its own rules for that
+    if (spans_overlap(w, ra) || spans_overlap(w, rb)) return SMHIP_OK;  // in place: the one-launch path has its own rules for that
     const bool same_inline = a_host_bytes && a == b && a_host_bytes == b_host_bytes;  // `ac + ac` on a host-built array: its bytes go in once
     const size_t need = sizeof(TinyOp) + ((a_host_bytes + 15) & ~(size_t)15) + (same_inline ? 0 : ((b_host_bytes + 15) & ~(size_t)15));
 
@@ -348,9 +343,9 @@ int tiny_try_enqueue(int op, int dtype, const void *a, size_t a_host_bytes, cons
         list = keep;
     };
     for (int i = 0; i < q.count && !two; ++i)
-        if (overlap(w, q.writes[i]) || overlap(ra, q.writes[i]) || overlap(rb, q.writes[i])) after(q.write_list[i]);  // WAW, RAW
+        if (spans_overlap(w, q.writes[i]) || spans_overlap(ra, q.writes[i]) || spans_overlap(rb, q.writes[i])) after(q.write_list[i]);  // WAW, RAW
     for (int i = 0; i < q.n_reads && !two; ++i)
-        if (overlap(w, q.reads[i])) after(q.read_list[i]);  // WAR
+        if (spans_overlap(w, q.reads[i])) after(q.read_list[i]);  // WAR
     if (two || q.count == kTinyMaxOps || q.used + need > (size_t)kTinyBigBytes) {
         if (int rc = flush_locked(q)) return rc;
         list = -1;

@@ -12,6 +12,8 @@
 // 4 * sizeof(T) bytes per element: five more Ops through every broadcast kernel was too much code for the rarer case.
 #include <type_traits>
 
+#include "abi_args.h"
+#include "axis_plan.h"
 #include "internal.h"
 #include "ops.hip.h"
 
@@ -79,21 +81,6 @@ int run_dense_fn(int fn, const void *a, void *out, size_t n, hipStream_t s) {
     return fail(SMHIP_ERR_UNSUPPORTED, "unary: function %d is not defined for an integer element type", fn);
 }
 
-size_t view_span_bytes(const int64_t *shape, const int64_t *strides, int ndim, size_t esz) {
-    int64_t last = 0;
-    for (int d = 0; d < ndim; ++d) last += (shape[d] - 1) * strides[d];
-    return (size_t)(last + 1) * esz;
-}
-
-bool dense_view(const int64_t *shape, const int64_t *strides, int ndim) {
-    int64_t expected = 1;
-    for (int d = ndim - 1; d >= 0; --d) {
-        if (shape[d] != 1 && strides[d] != expected) return false;
-        expected *= shape[d];
-    }
-    return true;
-}
-
 }  // namespace
 
 int launch_unary_dense(int fn, int dtype, const void *a, size_t n, void *out, hipStream_t s) {
@@ -116,7 +103,7 @@ int launch_unary(int fn, int dtype, const void *a, const int64_t *strides, const
     size_t n = 1;
     for (int d = 0; d < ndim; ++d) n *= (size_t)shape[d];
     if (n == 0) return SMHIP_OK;
-    if (dense_view(shape, strides, ndim)) return launch_unary_dense(fn, dtype, a, n, out, s);
+    if (axis_plan::row_major(shape, strides, ndim)) return launch_unary_dense(fn, dtype, a, n, out, s);
     const int64_t zero[SMHIP_MAX_NDIM] = {};
     if (fn == SMHIP_UNARY_EXP || fn == SMHIP_UNARY_LOG) {
         if (int rc = launch_broadcast(SMHIP_OP_LEFT, dtype, a, strides, a, zero, shape, ndim, out, s)) return rc;
@@ -143,13 +130,11 @@ int smhip_unary(int fn, int dtype, const void *a, const int64_t *strides, const 
     if (n == 0) return SMHIP_OK;
     if (!a || !out) return fail(SMHIP_ERR_INVALID, "unary: null buffer");
     const size_t esz = dtype_size(dtype);
-    const size_t a_bytes = view_span_bytes(shape, strides, ndim, esz), out_bytes = (size_t)n * esz;
-    const char *pa = static_cast<const char *>(a), *po = static_cast<const char *>(out);
-    if (pa < po + out_bytes && po < pa + a_bytes && !(pa == po && dense_view(shape, strides, ndim)))
+    const Span read{a, span_bytes(shape, strides, ndim, esz)}, write{out, (size_t)n * esz};
+    if (spans_overlap(read, write) && !(a == out && axis_plan::row_major(shape, strides, ndim)))
         return fail(SMHIP_ERR_INVALID, "unary: `out` overlaps the operand (only out == a with a dense operand is in place)");
     hipStream_t s;
     OpScope op_scope;
-    const Span read{a, a_bytes};
-    if (int rc = op_scope.begin(&read, 1, Span{out, out_bytes}, &s)) return rc;  // recorded tiny operators are flushed first
+    if (int rc = op_scope.begin(&read, 1, write, &s)) return rc;  // recorded tiny operators are flushed first
     return launch_unary(fn, dtype, a, strides, shape, ndim, out, s);
 }

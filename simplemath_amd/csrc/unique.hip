@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "abi_args.h"
 #include "axis_plan.h"
 #include "internal.h"
 #include "ops.hip.h"
@@ -310,12 +311,6 @@ int launch_runs(int what, int flags, int dtype, RunArgs g, hipStream_t s) {
     return fail(SMHIP_ERR_INVALID, "runs: bad dtype %d", dtype);
 }
 
-bool overlap(Span x, Span y) {
-    const char *x0 = static_cast<const char *>(x.p), *y0 = static_cast<const char *>(y.p);
-    return x.p && y.p && x.bytes && y.bytes && x0 < y0 + y.bytes && y0 < x0 + x.bytes;
-}
-bool misaligned(const void *p, size_t esz) { return (reinterpret_cast<uintptr_t>(p) & (esz - 1)) != 0; }
-
 // What can be said without a pointer: flags, dtype, n.
 int runs_check(const char *who, int flags, int dtype, int64_t n) {
     if (flags & ~SMHIP_RUNS_NAN_DISTINCT) return fail(SMHIP_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
@@ -336,7 +331,7 @@ int smhip_runs_count(int flags, int dtype, const void *s, int64_t n, int64_t *co
     if (n && !s) return fail(SMHIP_ERR_INVALID, "runs_count: null operand");
     const size_t esz = dtype_size(dtype);
     if (misaligned(s, esz) || misaligned(count_dev, sizeof(int64_t))) return fail(SMHIP_ERR_INVALID, "runs_count: a pointer is not aligned to its element");
-    if (overlap(Span{count_dev, sizeof(int64_t)}, Span{s, (size_t)n * esz})) return fail(SMHIP_ERR_INVALID, "runs_count: the result overlaps the operand");
+    if (spans_overlap(Span{count_dev, sizeof(int64_t)}, Span{s, (size_t)n * esz})) return fail(SMHIP_ERR_INVALID, "runs_count: the result overlaps the operand");
     hipStream_t st;
     OpScope op_scope;  // undeclared spans (the pooled counts): ordered behind everything, recorded tiny operators flushed first
     if (int rc = op_scope.begin_barrier(&st)) return rc;
@@ -365,7 +360,7 @@ int smhip_runs(int flags, int dtype, const void *s, int64_t n, const int64_t *or
     const char *names[7] = {"values_out", "index_out", "counts_out", "inverse_out", "count_dev", "s", "order"};
     for (int a = 0; a < 5; ++a)      // every span that is written ...
         for (int b = a + 1; b < 7; ++b)  // ... against every other one
-            if (overlap(spans[a], spans[b])) return fail(SMHIP_ERR_INVALID, "runs: %s overlaps %s", names[a], names[b]);
+            if (spans_overlap(spans[a], spans[b])) return fail(SMHIP_ERR_INVALID, "runs: %s overlaps %s", names[a], names[b]);
     const bool firsts = items && (values_out || index_out || counts_out);
     if (n == 0 || (!firsts && !inverse_out)) {  // nothing to write but, perhaps, the count
         if (!count_dev_or_null) return SMHIP_OK;
