@@ -34,6 +34,7 @@
 #include <functional>
 #include <initializer_list>
 #include <memory>
+#include <optional>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -335,6 +336,38 @@ inline std::vector<std::size_t> dense_strides(const std::vector<std::size_t> &sh
     return st;
 }
 
+// float, double, int and std::int64_t: the element types the axis, index, counting, condition and unique families have kernels for.
+template <typename T>
+inline constexpr bool four_types_v = hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64;
+
+// `axis` of an array of rank `nd`, counted from the end when negative.  Out of range: E, its message opened by the caller's `prefix`
+// (the reductions, scans, argmax / argmin and sort throw std::runtime_error, take and the scatters std::invalid_argument "take: ...").
+template <typename E>
+int normal_axis(int axis, std::size_t nd, const char *prefix = "") {
+    const int n = static_cast<int>(nd), a = axis < 0 ? axis + n : axis;
+    if (a < 0 || a >= n) throw E(std::string("simpleMath/MI355X: ") + prefix + "axis " + std::to_string(axis) + " out of range for rank " + std::to_string(n));
+    return a;
+}
+
+// One word of device memory that a library call writes and the host reads afterwards: a bad-index flag, a count, a sum.  Empty
+// (ptr() == nullptr, nothing taken from the pool) when nobody will read it.
+template <typename W = std::int64_t>
+class DeviceWord {
+public:
+    explicit DeviceWord(bool wanted = true) {
+        if (wanted) buf_ = hip::DeviceBuffer(sizeof(W));
+    }
+    W *ptr() const { return buf_.template as<W>(); }
+    explicit operator bool() const { return buf_.get() != nullptr; }
+    W read() const {  // waits for the stream
+        W v{};
+        hip::check(smhip_download(&v, buf_.get(), sizeof v));
+        return v;
+    }
+private:
+    hip::DeviceBuffer buf_;
+};
+
 }  // namespace detail
 
 template <ArithmeticOrComplex T>
@@ -499,26 +532,15 @@ public:
     // Dot product over all elements (reference SMArray.h:213-215 -> dot_product<T>).
     T operator%(const SMArray &arr) const {
         if (totalSize != arr.totalSize) throw std::runtime_error("dot product: element counts differ");
-        if constexpr (hip::dot_dtype_of<T>::id >= 0) {  // the four kernel types and the generic template's other integer types
-            hip::DeviceGuard on(common_device(*this, arr));
-            std::unique_ptr<SMArray> lhs_holder, rhs_holder;
-            const T *pa = dense_device(lhs_holder), *pb = arr.dense_device(rhs_holder);
-            return hip::dot_device<T>(pa, pb, totalSize);
-        } else if constexpr (std::is_same_v<T, std::complex<double>>) {
-            // complex arrays are as resident as any other (16-byte elements in the same Storage): device pointers in, no host staging
-            hip::DeviceGuard on(common_device(*this, arr));
-            std::unique_ptr<SMArray> lhs_holder, rhs_holder;
-            const T *pa = dense_device(lhs_holder), *pb = arr.dense_device(rhs_holder);
-            return hip::dot_device_c64(pa, pb, totalSize);
-        } else if constexpr (std::is_same_v<T, std::complex<float>>) {  // the generic template's instantiation, on resident arrays
-            hip::DeviceGuard on(common_device(*this, arr));
-            std::unique_ptr<SMArray> lhs_holder, rhs_holder;
-            const T *pa = dense_device(lhs_holder), *pb = arr.dense_device(rhs_holder);
-            return hip::dot_device_c32(pa, pb, totalSize);
-        } else {
-            static_assert(dependent_false<T>::value, "operator%: this element type has no gfx950 dot-product kernel (float, double, every "
-                                                     "8- to 64-bit integer type, std::complex<float> and std::complex<double> do)");
-        }
+        constexpr bool c64 = std::is_same_v<T, std::complex<double>>, c32 = std::is_same_v<T, std::complex<float>>;
+        static_assert(hip::dot_dtype_of<T>::id >= 0 || c64 || c32, "operator%: this element type has no gfx950 dot-product kernel (float, double, every "
+                                                                   "8- to 64-bit integer type, std::complex<float> and std::complex<double> do)");
+        // complex arrays are as resident as any other (16-byte elements in the same Storage): device pointers in, no host staging
+        hip::DeviceGuard on(common_device(*this, arr));
+        const AbiView a = flat(), b = arr.flat();
+        if constexpr (c64) return hip::dot_device_c64(a.ptr, b.ptr, totalSize);
+        else if constexpr (c32) return hip::dot_device_c32(a.ptr, b.ptr, totalSize);  // the generic template's instantiation, on resident arrays
+        else return hip::dot_device<T>(a.ptr, b.ptr, totalSize);  // the four kernel types and the generic template's other integer types
     }
 
     // + - * / with an array (NumPy broadcasting) or a scalar: reference SMArray.h:217-305.  The argument types convert
@@ -750,10 +772,9 @@ public:
     double sum() const & {
         static_assert(hip::dtype_of<T>::id >= 0, "sum(): element type has no kernels");
         hip::DeviceGuard on(device());
-        std::unique_ptr<SMArray> holder;
-        const T *p = dense_device(holder);
+        const AbiView in = flat();
         double s = 0;
-        hip::check(smhip_sum(hip::dtype_of<T>::id, p, totalSize, &s));
+        hip::check(smhip_sum(hip::dtype_of<T>::id, in.ptr, totalSize, &s));
         return s;
     }
 
@@ -786,14 +807,14 @@ public:
     // are scanned in row-major order and the result has shape {totalSize}, as np.cumsum(a) does.  A pending operator chain as
     // the operand is evaluated first; the scan is ONE smhip_scan_axis call (counted in sm::fusion_stats().scans) and its
     // result feeds the next chain like any array: `h.cumsum(0) / h.sum(0, true)` is a CDF.
-    SMArray cumsum(int axis) const { return scan_along(SMHIP_SCAN_SUM, axis); }
-    SMArray cumprod(int axis) const { return scan_along(SMHIP_SCAN_PROD, axis); }
-    SMArray cummax(int axis) const { return scan_along(SMHIP_SCAN_MAX, axis); }
-    SMArray cummin(int axis) const { return scan_along(SMHIP_SCAN_MIN, axis); }
-    SMArray cumsum() const { return scan_flat(SMHIP_SCAN_SUM); }
-    SMArray cumprod() const { return scan_flat(SMHIP_SCAN_PROD); }
-    SMArray cummax() const { return scan_flat(SMHIP_SCAN_MAX); }
-    SMArray cummin() const { return scan_flat(SMHIP_SCAN_MIN); }
+    SMArray cumsum(int axis) const { return scan_of(SMHIP_SCAN_SUM, axis); }
+    SMArray cumprod(int axis) const { return scan_of(SMHIP_SCAN_PROD, axis); }
+    SMArray cummax(int axis) const { return scan_of(SMHIP_SCAN_MAX, axis); }
+    SMArray cummin(int axis) const { return scan_of(SMHIP_SCAN_MIN, axis); }
+    SMArray cumsum() const { return scan_of(SMHIP_SCAN_SUM, std::nullopt); }
+    SMArray cumprod() const { return scan_of(SMHIP_SCAN_PROD, std::nullopt); }
+    SMArray cummax() const { return scan_of(SMHIP_SCAN_MAX, std::nullopt); }
+    SMArray cummin() const { return scan_of(SMHIP_SCAN_MIN, std::nullopt); }
 
     // WHERE the maximum / minimum along an axis stands (np.argmax / np.argmin): positions along `axis` as std::int64_t, the
     // first one on a tie (-0 == +0) and the first NaN if the axis holds one; resident on the device.  `axis` counts from the
@@ -802,12 +823,12 @@ public:
     // A pending operator chain as the operand is evaluated first, a transposed view is read in place; ONE
     // smhip_argreduce_axis call (counted in sm::fusion_stats().arg_reductions).  max_with_index / min_with_index give
     // {the extreme itself, its position} from the same single pass; the value is exactly the element at that position.
-    SMArray<std::int64_t> argmax(int axis, bool keepdims = false) const { return arg_along(SMHIP_ARG_MAX, axis, keepdims, nullptr); }
-    SMArray<std::int64_t> argmin(int axis, bool keepdims = false) const { return arg_along(SMHIP_ARG_MIN, axis, keepdims, nullptr); }
-    SMArray<std::int64_t> argmax() const { return arg_flat(SMHIP_ARG_MAX); }
-    SMArray<std::int64_t> argmin() const { return arg_flat(SMHIP_ARG_MIN); }
-    std::pair<SMArray, SMArray<std::int64_t>> max_with_index(int axis, bool keepdims = false) const { return arg_with_value(SMHIP_ARG_MAX, axis, keepdims); }
-    std::pair<SMArray, SMArray<std::int64_t>> min_with_index(int axis, bool keepdims = false) const { return arg_with_value(SMHIP_ARG_MIN, axis, keepdims); }
+    SMArray<std::int64_t> argmax(int axis, bool keepdims = false) const { return arg_of(SMHIP_ARG_MAX, axis, keepdims, false).second; }
+    SMArray<std::int64_t> argmin(int axis, bool keepdims = false) const { return arg_of(SMHIP_ARG_MIN, axis, keepdims, false).second; }
+    SMArray<std::int64_t> argmax() const { return arg_of(SMHIP_ARG_MAX, std::nullopt, false, false).second; }
+    SMArray<std::int64_t> argmin() const { return arg_of(SMHIP_ARG_MIN, std::nullopt, false, false).second; }
+    std::pair<SMArray, SMArray<std::int64_t>> max_with_index(int axis, bool keepdims = false) const { return arg_of(SMHIP_ARG_MAX, axis, keepdims, true); }
+    std::pair<SMArray, SMArray<std::int64_t>> min_with_index(int axis, bool keepdims = false) const { return arg_of(SMHIP_ARG_MIN, axis, keepdims, true); }
 
     // The ORDER along an axis (np.sort / np.argsort with kind="stable"): sort gives the elements of each line in order, argsort
     // their positions along `axis` as std::int64_t; both have this array's shape and are resident on the device.  Ascending puts
@@ -819,32 +840,11 @@ public:
     // evaluated first; each is ONE smhip_sort_axis call (counted in sm::fusion_stats().sorts), sort_with_index giving {values,
     // positions} from the same call.  The result feeds the next chain or a slice like any array: `x.sort(-1)(SLICE_ALL,
     // SLICE(0, 5))` is a view of the five smallest of each row.
-    SMArray sort(int axis = -1, bool descending = false) const {
-        SMArray values = device_empty(std::vector<std::size_t>(_shape));
-        sort_along(axis, descending, &values, nullptr);
-        return values;
-    }
-    SMArray<std::int64_t> argsort(int axis = -1, bool descending = false) const {
-        SMArray<std::int64_t> where = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>(_shape));
-        sort_along(axis, descending, nullptr, &where);
-        return where;
-    }
-    std::pair<SMArray, SMArray<std::int64_t>> sort_with_index(int axis = -1, bool descending = false) const {
-        SMArray values = device_empty(std::vector<std::size_t>(_shape));
-        SMArray<std::int64_t> where = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>(_shape));
-        sort_along(axis, descending, &values, &where);
-        return {std::move(values), std::move(where)};
-    }
-    SMArray sort_flat(bool descending = false) const {
-        SMArray values = device_empty(std::vector<std::size_t>{totalSize});
-        sort_all(descending, &values, nullptr);
-        return values;
-    }
-    SMArray<std::int64_t> argsort_flat(bool descending = false) const {
-        SMArray<std::int64_t> where = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{totalSize});
-        sort_all(descending, nullptr, &where);
-        return where;
-    }
+    SMArray sort(int axis = -1, bool descending = false) const { return sort_of(axis, descending, true, false).first; }
+    SMArray<std::int64_t> argsort(int axis = -1, bool descending = false) const { return sort_of(axis, descending, false, true).second; }
+    std::pair<SMArray, SMArray<std::int64_t>> sort_with_index(int axis = -1, bool descending = false) const { return sort_of(axis, descending, true, true); }
+    SMArray sort_flat(bool descending = false) const { return sort_of(std::nullopt, descending, true, false).first; }
+    SMArray<std::int64_t> argsort_flat(bool descending = false) const { return sort_of(std::nullopt, descending, false, true).second; }
 
     // PICKING BY POSITION along an axis (np.take_along_axis / np.take): the consumer of what argmax, argsort and sort_with_index
     // produce.  take_along_axis: `idx` is an SMArray<std::int64_t> of this array's rank whose other axes equal this array's
@@ -862,7 +862,7 @@ public:
         if (idx.shape().size() != nd)
             throw std::invalid_argument("simpleMath/MI355X: take_along_axis: the index array has rank " + std::to_string(idx.shape().size()) +
                                         ", the operand rank " + std::to_string(nd));
-        const int ax = take_axis_of(axis, nd);
+        const int ax = detail::normal_axis<std::invalid_argument>(axis, nd, "take: ");
         hip::DeviceGuard on(device());
         std::vector<std::int64_t> shape(nd), sa(nd), si(nd);
         std::vector<std::size_t> result(nd);
@@ -887,7 +887,7 @@ public:
     SMArray take(const SMArray<std::int64_t> &idx, int axis, index_mode mode = index_mode::checked) const {
         if (idx.shape().size() != 1) throw std::invalid_argument("simpleMath/MI355X: take: the index array must be 1-D");
         const std::size_t nd = _shape.size();
-        const int ax = take_axis_of(axis, nd);
+        const int ax = detail::normal_axis<std::invalid_argument>(axis, nd, "take: ");
         hip::DeviceGuard on(device());
         std::vector<std::int64_t> shape = hip::to_i64(_shape), sa = hip::to_i64(_strides), si(nd, 0);
         std::vector<std::size_t> result(_shape);
@@ -977,17 +977,15 @@ public:
     // negative count, a table that is not 1-D, and where numpy raises for a range -- bins < 1, lo or hi not finite, lo > hi, edges
     // that do not increase once rounded to T.  Each is ONE library call (sm::fusion_stats().counts).
     SMArray<std::int64_t> searchsorted(const SMArray &x, side s = side::left) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "searchsorted: f32, f64, i32 and i64");
+        static_assert(detail::four_types_v<T>, "searchsorted: f32, f64, i32 and i64");
         if (_shape.size() != 1) throw std::invalid_argument("simpleMath/MI355X: searchsorted: the edges must be 1-D");
         hip::DeviceGuard on(common_device(*this, x));
-        std::unique_ptr<SMArray> holder;
-        const T *edges = dense_device(holder);
-        const T *in = x.device_data();  // a pending chain that produces the operand runs here
-        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>(x._shape));
+        const AbiView edges = flat();
+        const AbiView in = x.along_axis(0);  // a pending chain that produces the operand runs here
+        Index out = Index::device_empty(std::vector<std::size_t>(x._shape));
         if (out.totalSize == 0) return out;
-        const auto sh = hip::to_i64(x._shape), st = hip::to_i64(x._strides);
-        hip::check(smhip_searchsorted(static_cast<int>(s), hip::dtype_of<T>::id, edges, static_cast<std::int64_t>(totalSize), in, sh.data(), st.data(),
-                                      static_cast<int>(sh.size()), out.device_data_mut()));
+        hip::check(smhip_searchsorted(static_cast<int>(s), hip::dtype_of<T>::id, edges.ptr, static_cast<std::int64_t>(totalSize), in.ptr, in.shape.data(),
+                                      in.strides.data(), in.ndim(), out.device_data_mut()));
         ++detail::tls_fusion_stats.counts;
         return out;
     }
@@ -996,21 +994,14 @@ public:
         if (nbins < 0 || (nbins == 0 && totalSize != 0))
             throw std::invalid_argument("simpleMath/MI355X: bincount: cannot count " + std::to_string(totalSize) + " ids into " + std::to_string(nbins) + " bins");
         hip::DeviceGuard on(device());
-        const T *ids = device_data();  // a pending chain that produces the ids runs here
-        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{static_cast<std::size_t>(nbins)});
+        const AbiView ids = along_axis(0);  // a pending chain that produces the ids runs here
+        Index out = Index::device_empty(std::vector<std::size_t>{static_cast<std::size_t>(nbins)});
         if (nbins == 0) return out;
-        const bool checked = mode == index_mode::checked && totalSize != 0;
-        hip::DeviceBuffer flag;  // one word from the pool, only when someone will read it
-        if (checked) flag = hip::DeviceBuffer(sizeof(std::int64_t));
-        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
-        hip::check(smhip_bincount(static_cast<int>(mode), hip::dtype_of<T>::id, ids, sh.data(), st.data(), static_cast<int>(sh.size()), nbins,
-                                  out.device_data_mut(), flag.template as<std::int64_t>()));
+        const detail::DeviceWord<> flag(mode == index_mode::checked && totalSize != 0);  // only when someone will read it
+        hip::check(smhip_bincount(static_cast<int>(mode), hip::dtype_of<T>::id, ids.ptr, ids.shape.data(), ids.strides.data(), ids.ndim(), nbins,
+                                  out.device_data_mut(), flag.ptr()));
         ++detail::tls_fusion_stats.counts;
-        if (checked) {
-            std::int64_t bad = 0;
-            hip::check(smhip_download(&bad, flag.get(), sizeof bad));  // waits for the stream
-            if (bad) throw std::out_of_range("simpleMath/MI355X: bincount: an id is out of bounds for " + std::to_string(nbins) + " bins");
-        }
+        if (flag && flag.read()) throw std::out_of_range("simpleMath/MI355X: bincount: an id is out of bounds for " + std::to_string(nbins) + " bins");
         return out;
     }
     std::pair<SMArray<std::int64_t>, SMArray> histogram(std::int64_t bins, double lo, double hi) const {
@@ -1020,7 +1011,7 @@ public:
         if (rc == SMHIP_ERR_INVALID) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + smhip_last_error());
         hip::check(rc);
         SMArray edges(table.release(), std::vector<std::size_t>{static_cast<std::size_t>(bins) + 1});
-        SMArray<std::int64_t> counts = count_between(edges, SMHIP_HISTOGRAM_UNIFORM, lo, hi);
+        Index counts = count_between(edges, SMHIP_HISTOGRAM_UNIFORM, lo, hi);
         return {std::move(counts), std::move(edges)};
     }
     SMArray<std::int64_t> histogram(const SMArray &edges) const {
@@ -1114,6 +1105,10 @@ private:
     friend struct detail::Chain<T>;
     template <typename U>
     friend struct Cond;
+    template <ArithmeticOrComplex U>
+    friend class SMArray;  // an operand of another element type (the index arrays) is seen through its own flat()
+
+    using Index = SMArray<std::int64_t>;  // positions, counts
 
     // Another handle on the same elements (same storage, offset, shape, strides): what a recorded chain keeps of an operand.
     SMArray alias() const {
@@ -1167,7 +1162,7 @@ public:
     // chain (smhip.h: SMHIP_OP_UNARY_BASE; counted in sm::fusion_stats() like any stage), exactly as pow_of continues it.  Of
     // anything else -- a named array, a view -- it launches smhip_unary, which reads views in place; the result lives in HBM.
     static SMArray unary_of(const SMArray &x, bool x_temporary, int fn) {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "sm::exp / log / sqrt / abs / unary minus: f32, f64, i32 and i64 arrays");
+        static_assert(detail::four_types_v<T>, "sm::exp / log / sqrt / abs / unary minus: f32, f64, i32 and i64 arrays");
         if (x_temporary) {
             if (detail::Chain<T> *cx = x.continuable()) {
                 hip::DeviceGuard on(x.device());
@@ -1199,8 +1194,8 @@ public:
     // result feeds the next chain like any device-born array; no host mirror is touched.  Asynchronous.
     template <typename U>
     SMArray<U> astype() const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "astype: the array's element type must be float, double, int or std::int64_t");
-        static_assert(hip::dtype_of<U>::id >= 0 && hip::dtype_of<U>::id <= SMHIP_I64, "astype<U>: U must be float, double, int or std::int64_t");
+        static_assert(detail::four_types_v<T>, "astype: the array's element type must be float, double, int or std::int64_t");
+        static_assert(detail::four_types_v<U>, "astype<U>: U must be float, double, int or std::int64_t");
         hip::DeviceGuard on(device());
         const T *in = device_data();  // a pending chain that produces this operand runs here
         SMArray<U> out = SMArray<U>::device_empty(std::vector<std::size_t>(_shape));
@@ -1338,172 +1333,133 @@ private:
         return bytes <= SMHIP_INLINE_MAX_BYTES ? bytes : 0;
     }
 
-    SMArray reduce_along(int kind, std::initializer_list<int> axes, bool keepdims) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "axis reductions: f32, f64, i32 and i64");
-        const int nd = static_cast<int>(_shape.size());
-        std::uint32_t mask = 0;
-        for (int ax : axes) {
-            const int a = ax < 0 ? ax + nd : ax;
-            if (a < 0 || a >= nd) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(ax) + " out of range for rank " + std::to_string(nd));
-            if (mask >> a & 1u) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(ax) + " repeated");
-            mask |= 1u << a;
-        }
-        if (!mask) throw std::runtime_error("simpleMath/MI355X: no axis to reduce");
+    // ---- the front's rules for the axis, index and counting families, each written once
+    // This array's shape without the axes that `mask` names (keepdims: with an extent of 1 in their place); {1} when nothing is left.
+    std::vector<std::size_t> kept_shape(std::uint32_t mask, bool keepdims) const {
         std::vector<std::size_t> shape;
-        for (int d = 0; d < nd; ++d) {
+        for (std::size_t d = 0; d < _shape.size(); ++d) {
             if (!(mask >> d & 1u)) shape.push_back(_shape[d]);
-            else if (keepdims) shape.push_back(1);
-        }
-        if (shape.empty()) shape.push_back(1);
-        hip::DeviceGuard on(device());
-        const T *in = device_data();  // a pending chain that produces this operand runs here
-        SMArray out = device_empty(std::move(shape));
-        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
-        hip::check(smhip_reduce_axes(kind, hip::dtype_of<T>::id, in, sh.data(), st.data(), nd, mask, out.device_data_mut()));
-        ++detail::tls_fusion_stats.reductions;
-        return out;
-    }
-
-    SMArray scan_along(int kind, int axis) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "cumulative scans: f32, f64, i32 and i64");
-        const int nd = static_cast<int>(_shape.size());
-        const int a = axis < 0 ? axis + nd : axis;
-        if (a < 0 || a >= nd) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(axis) + " out of range for rank " + std::to_string(nd));
-        hip::DeviceGuard on(device());
-        const T *in = device_data();  // a pending chain that produces this operand runs here
-        SMArray out = device_empty(std::vector<std::size_t>(_shape));
-        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
-        hip::check(smhip_scan_axis(kind, hip::dtype_of<T>::id, in, sh.data(), st.data(), nd, a, out.device_data_mut()));
-        ++detail::tls_fusion_stats.scans;
-        return out;
-    }
-    // The elements in row-major order as one row: a view is made dense first.
-    SMArray scan_flat(int kind) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "cumulative scans: f32, f64, i32 and i64");
-        hip::DeviceGuard on(device());
-        std::unique_ptr<SMArray> holder;
-        const T *in = dense_device(holder);
-        SMArray out = device_empty(std::vector<std::size_t>{totalSize});
-        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
-        hip::check(smhip_scan_axis(kind, hip::dtype_of<T>::id, in, &n, &one, 1, 0, out.device_data_mut()));
-        ++detail::tls_fusion_stats.scans;
-        return out;
-    }
-
-    int arg_axis(int axis) const {
-        const int nd = static_cast<int>(_shape.size());
-        const int a = axis < 0 ? axis + nd : axis;
-        if (a < 0 || a >= nd) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(axis) + " out of range for rank " + std::to_string(nd));
-        return a;
-    }
-    std::vector<std::size_t> arg_shape(int axis, bool keepdims) const {
-        const int a = arg_axis(axis);
-        std::vector<std::size_t> shape;
-        for (int d = 0; d < static_cast<int>(_shape.size()); ++d) {
-            if (d != a) shape.push_back(_shape[d]);
             else if (keepdims) shape.push_back(1);
         }
         if (shape.empty()) shape.push_back(1);
         return shape;
     }
-    std::pair<SMArray, SMArray<std::int64_t>> arg_with_value(int kind, int axis, bool keepdims) const {
-        SMArray values = device_empty(arg_shape(axis, keepdims));
-        SMArray<std::int64_t> where = arg_along(kind, axis, keepdims, &values);
-        return {std::move(values), std::move(where)};
+    // An operand as the C ABI takes it: the device pointer (building one is where a pending chain that produces the operand runs),
+    // shape and strides in elements, the axis the call runs along, and the dense copy the pointer belongs to if one had to be made.
+    struct AbiView {
+        const T *ptr = nullptr;
+        std::vector<std::int64_t> shape, strides;
+        int axis = 0;
+        std::unique_ptr<SMArray> dense;
+        int ndim() const { return static_cast<int>(shape.size()); }
+    };
+    // ... along `axis` (already normalised; 0 for a call that names none) of this view, read in place.
+    AbiView along_axis(int axis) const { return AbiView{device_data(), hip::to_i64(_shape), hip::to_i64(_strides), axis, nullptr}; }
+    // ... as its row-major flattening, one line of totalSize elements: a view that is not dense is copied dense first.
+    AbiView flat() const {
+        AbiView v;
+        if (!is_dense()) v.dense.reset(new SMArray(contiguous()));
+        v.ptr = v.dense ? v.dense->device_data() : device_data();
+        v.shape = {static_cast<std::int64_t>(totalSize)}, v.strides = {1};
+        return v;
     }
-    // `values`: a dense array of the result's shape for the extremes themselves, or nullptr.
-    SMArray<std::int64_t> arg_along(int kind, int axis, bool keepdims, SMArray *values) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "argmax / argmin: f32, f64, i32 and i64");
-        const int a = arg_axis(axis);
-        hip::DeviceGuard on(device());
-        const T *in = device_data();  // a pending chain that produces this operand runs here
-        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(arg_shape(axis, keepdims));
-        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
-        hip::check(smhip_argreduce_axis(kind, hip::dtype_of<T>::id, in, sh.data(), st.data(), static_cast<int>(sh.size()), a, out.device_data_mut(),
-                                        values ? values->device_data_mut() : nullptr));
-        ++detail::tls_fusion_stats.arg_reductions;
-        return out;
+    // ... along an axis (counted from the end when negative; std::runtime_error out of range), or flattened when there is none.
+    // The axis is checked before anything touches the device.
+    std::optional<int> line_axis(std::optional<int> axis) const {
+        if (axis) axis = detail::normal_axis<std::runtime_error>(*axis, _shape.size());
+        return axis;
     }
-    // The elements in row-major order as one row: a view is made dense first.
-    SMArray<std::int64_t> arg_flat(int kind) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "argmax / argmin: f32, f64, i32 and i64");
+    AbiView line(std::optional<int> axis) const { return axis ? along_axis(*axis) : flat(); }
+
+    SMArray reduce_along(int kind, std::initializer_list<int> axes, bool keepdims) const {
+        static_assert(detail::four_types_v<T>, "axis reductions: f32, f64, i32 and i64");
+        std::uint32_t mask = 0;
+        for (int ax : axes) {
+            const int a = detail::normal_axis<std::runtime_error>(ax, _shape.size());
+            if (mask >> a & 1u) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(ax) + " repeated");
+            mask |= 1u << a;
+        }
+        if (!mask) throw std::runtime_error("simpleMath/MI355X: no axis to reduce");
+        std::vector<std::size_t> shape = kept_shape(mask, keepdims);
         hip::DeviceGuard on(device());
-        std::unique_ptr<SMArray> holder;
-        const T *in = dense_device(holder);
-        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{1});
-        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
-        hip::check(smhip_argreduce_axis(kind, hip::dtype_of<T>::id, in, &n, &one, 1, 0, out.device_data_mut(), nullptr));
-        ++detail::tls_fusion_stats.arg_reductions;
+        const AbiView in = along_axis(0);  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(std::move(shape));
+        hip::check(smhip_reduce_axes(kind, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), mask, out.device_data_mut()));
+        ++detail::tls_fusion_stats.reductions;
         return out;
     }
 
-    // `values` / `where`: dense arrays of this array's shape for the sorted elements / their positions; either may be nullptr.
-    void sort_along(int axis, bool descending, SMArray *values, SMArray<std::int64_t> *where) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "sort / argsort: f32, f64, i32 and i64");
-        const int a = arg_axis(axis);
+    // Without an axis: the elements in row-major order as one line, shape {totalSize}.
+    SMArray scan_of(int kind, std::optional<int> axis) const {
+        static_assert(detail::four_types_v<T>, "cumulative scans: f32, f64, i32 and i64");
+        axis = line_axis(axis);
         hip::DeviceGuard on(device());
-        const T *in = device_data();  // a pending chain that produces this operand runs here
-        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
-        hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, sh.data(), st.data(),
-                                   static_cast<int>(sh.size()), a, values ? values->device_data_mut() : nullptr, where ? where->device_data_mut() : nullptr));
-        ++detail::tls_fusion_stats.sorts;
-    }
-    // The elements in row-major order as one line: a view is made dense first.
-    void sort_all(bool descending, SMArray *values, SMArray<std::int64_t> *where) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "sort / argsort: f32, f64, i32 and i64");
-        hip::DeviceGuard on(device());
-        std::unique_ptr<SMArray> holder;
-        const T *in = dense_device(holder);
-        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
-        hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, &n, &one, 1, 0,
-                                   values ? values->device_data_mut() : nullptr, where ? where->device_data_mut() : nullptr));
-        ++detail::tls_fusion_stats.sorts;
+        const AbiView in = line(axis);  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(axis ? std::vector<std::size_t>(_shape) : std::vector<std::size_t>{totalSize});
+        hip::check(smhip_scan_axis(kind, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), in.axis, out.device_data_mut()));
+        ++detail::tls_fusion_stats.scans;
+        return out;
     }
 
-    static int take_axis_of(int axis, std::size_t nd) {
-        const int n = static_cast<int>(nd), a = axis < 0 ? axis + n : axis;
-        if (a < 0 || a >= n) throw std::invalid_argument("simpleMath/MI355X: take: axis " + std::to_string(axis) + " out of range for rank " + std::to_string(n));
-        return a;
+    // {the extremes themselves, their positions}, of the kept shape (without an axis: the row-major index into this array, shape {1});
+    // the values have shape {0} when they are not wanted.
+    std::pair<SMArray, Index> arg_of(int kind, std::optional<int> axis, bool keepdims, bool want_values) const {
+        static_assert(detail::four_types_v<T>, "argmax / argmin: f32, f64, i32 and i64");
+        axis = line_axis(axis);
+        hip::DeviceGuard on(device());
+        const AbiView in = line(axis);  // a pending chain that produces this operand runs here
+        const std::vector<std::size_t> shape = axis ? kept_shape(1u << *axis, keepdims) : std::vector<std::size_t>{1};
+        std::pair<SMArray, Index> r{device_empty(want_values ? std::vector<std::size_t>(shape) : std::vector<std::size_t>{0}), Index::device_empty(std::vector<std::size_t>(shape))};
+        hip::check(smhip_argreduce_axis(kind, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), in.axis, r.second.device_data_mut(),
+                                        want_values ? r.first.device_data_mut() : nullptr));
+        ++detail::tls_fusion_stats.arg_reductions;
+        return r;
     }
+
+    // {the sorted elements, their positions}, of this array's shape (without an axis: of {totalSize}); one that is not wanted has shape {0}.
+    std::pair<SMArray, Index> sort_of(std::optional<int> axis, bool descending, bool want_values, bool want_where) const {
+        static_assert(detail::four_types_v<T>, "sort / argsort: f32, f64, i32 and i64");
+        axis = line_axis(axis);
+        hip::DeviceGuard on(device());
+        const AbiView in = line(axis);  // a pending chain that produces this operand runs here
+        const auto shape = [&](bool wanted) { return !wanted ? std::vector<std::size_t>{0} : axis ? _shape : std::vector<std::size_t>{totalSize}; };
+        std::pair<SMArray, Index> r{device_empty(shape(want_values)), Index::device_empty(shape(want_where))};
+        hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(),
+                                   in.ndim(), in.axis, want_values ? r.first.device_data_mut() : nullptr, want_where ? r.second.device_data_mut() : nullptr));
+        ++detail::tls_fusion_stats.sorts;
+        return r;
+    }
+
     // Both operands in row-major order as one line each (views are made dense first), shape {idx.size()}.
-    SMArray take_flat_of(const SMArray<std::int64_t> &idx, index_mode mode) const {
+    SMArray take_flat_of(const Index &idx, index_mode mode) const {
         hip::DeviceGuard on(device());
-        std::unique_ptr<SMArray> holder;
-        const T *in = dense_device(holder);
-        std::unique_ptr<SMArray<std::int64_t>> idx_holder;
-        if (!idx.is_dense()) idx_holder.reset(new SMArray<std::int64_t>(idx.contiguous()));
-        const std::int64_t *ix = idx_holder ? idx_holder->device_data() : idx.device_data();
-        const std::vector<std::int64_t> shape{static_cast<std::int64_t>(idx.totalSize)}, one{1};
-        return take_run(in, ix, shape, one, one, 0, totalSize, mode, std::vector<std::size_t>{idx.totalSize});
+        const AbiView in = flat();
+        const typename Index::AbiView ix = idx.flat();
+        return take_run(in.ptr, ix.ptr, ix.shape, in.strides, ix.strides, 0, totalSize, mode, std::vector<std::size_t>{idx.totalSize});
     }
     // `in` / `ix`: device pointers to the operands' first elements, pending chains already evaluated.
     SMArray take_run(const T *in, const std::int64_t *ix, const std::vector<std::int64_t> &shape, const std::vector<std::int64_t> &sa,
                      const std::vector<std::int64_t> &si, int axis, std::size_t extent, index_mode mode, std::vector<std::size_t> &&result) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "take / take_along_axis: f32, f64, i32 and i64");
+        static_assert(detail::four_types_v<T>, "take / take_along_axis: f32, f64, i32 and i64");
         hip::DeviceGuard on(device());
         SMArray out = device_empty(std::move(result));
         if (out.totalSize == 0) return out;
         if (extent == 0) throw std::out_of_range("simpleMath/MI355X: take: cannot take from an axis of 0 elements");
-        hip::DeviceBuffer flag;  // one word from the pool, only when someone will read it
-        if (mode == index_mode::checked) flag = hip::DeviceBuffer(sizeof(std::int64_t));
+        const detail::DeviceWord<> flag(mode == index_mode::checked);  // only when someone will read it
         hip::check(smhip_take_axis(static_cast<int>(mode), hip::dtype_of<T>::id, in, sa.data(), static_cast<std::int64_t>(extent), ix, si.data(), shape.data(),
-                                   static_cast<int>(shape.size()), axis, out.device_data_mut(), flag.template as<std::int64_t>()));
+                                   static_cast<int>(shape.size()), axis, out.device_data_mut(), flag.ptr()));
         ++detail::tls_fusion_stats.takes;
-        if (mode == index_mode::checked) {
-            std::int64_t bad = 0;
-            hip::check(smhip_download(&bad, flag.get(), sizeof bad));  // waits for the stream
-            if (bad) throw std::out_of_range("simpleMath/MI355X: take: an index is out of bounds for an axis of " + std::to_string(extent) + " elements");
-        }
+        if (flag && flag.read()) throw std::out_of_range("simpleMath/MI355X: take: an index is out of bounds for an axis of " + std::to_string(extent) + " elements");
         return out;
     }
 
     // ---- scatter: the walk shape is this array's shape with `axis` replaced by the entries per line
-    SMArray &scatter_along(int kind, const SMArray<std::int64_t> &idx, const SMArray *values, T scalar, int axis, index_mode mode, bool unique) {
+    SMArray &scatter_along(int kind, const Index &idx, const SMArray *values, T scalar, int axis, index_mode mode, bool unique) {
         const std::size_t nd = _shape.size();
         if (idx.shape().size() != nd)
             throw std::invalid_argument("simpleMath/MI355X: put_along_axis / scatter_add: the index array has rank " + std::to_string(idx.shape().size()) +
                                         ", the target rank " + std::to_string(nd));
-        const int ax = take_axis_of(axis, nd);
+        const int ax = detail::normal_axis<std::invalid_argument>(axis, nd, "take: ");
         std::vector<std::int64_t> walk(nd), si(nd);
         for (std::size_t d = 0; d < nd; ++d) {
             const std::size_t na = _shape[d], ni = idx.shape()[d];
@@ -1515,19 +1471,19 @@ private:
         }
         return scatter_run(kind, walk, ax, idx, si, values, scalar, mode, unique);
     }
-    SMArray &scatter_ids(int kind, const SMArray<std::int64_t> &ids, const SMArray *values, T scalar, int axis, index_mode mode, bool unique) {
+    SMArray &scatter_ids(int kind, const Index &ids, const SMArray *values, T scalar, int axis, index_mode mode, bool unique) {
         if (ids.shape().size() != 1) throw std::invalid_argument("simpleMath/MI355X: put / index_add: the index array must be 1-D");
         const std::size_t nd = _shape.size();
-        const int ax = take_axis_of(axis, nd);
+        const int ax = detail::normal_axis<std::invalid_argument>(axis, nd, "take: ");
         std::vector<std::int64_t> walk = hip::to_i64(_shape), si(nd, 0);
         walk[ax] = static_cast<std::int64_t>(ids.totalSize), si[ax] = static_cast<std::int64_t>(ids.strides()[0]);
         return scatter_run(kind, walk, ax, ids, si, values, scalar, mode, unique);
     }
     // This array and idx in row-major order as one line each.
-    SMArray &scatter_flat(int kind, const SMArray<std::int64_t> &idx, const SMArray *values, T scalar, index_mode mode, bool unique) {
+    SMArray &scatter_flat(int kind, const Index &idx, const SMArray *values, T scalar, index_mode mode, bool unique) {
         if (!is_dense()) return staged([&](SMArray &dense) { dense.scatter_flat(kind, idx, values, scalar, mode, unique); });
-        std::unique_ptr<SMArray<std::int64_t>> idx_holder;
-        if (!idx.is_dense()) idx_holder.reset(new SMArray<std::int64_t>(idx.contiguous()));
+        std::unique_ptr<Index> idx_holder;
+        if (!idx.is_dense()) idx_holder.reset(new Index(idx.contiguous()));
         std::unique_ptr<SMArray> val_line;
         if (values) {
             val_line.reset(new SMArray(values->is_dense() ? values->alias() : values->contiguous()));
@@ -1553,9 +1509,9 @@ private:
         *this = std::move(dense);
         return *this;
     }
-    SMArray &scatter_run(int kind, const std::vector<std::int64_t> &walk, int axis, const SMArray<std::int64_t> &idx, const std::vector<std::int64_t> &si,
+    SMArray &scatter_run(int kind, const std::vector<std::int64_t> &walk, int axis, const Index &idx, const std::vector<std::int64_t> &si,
                          const SMArray *values, T scalar, index_mode mode, bool unique) {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "put / put_along_axis / scatter_add / index_add: f32, f64, i32 and i64");
+        static_assert(detail::four_types_v<T>, "put / put_along_axis / scatter_add / index_add: f32, f64, i32 and i64");
         const std::size_t nd = walk.size();
         // values against the walk shape, aligned at the last axis
         std::vector<std::int64_t> sv(nd, 0);
@@ -1577,7 +1533,7 @@ private:
         hip::DeviceGuard on(device());
         // an operand that shares the target's storage is copied first: the C ABI refuses the overlap
         std::unique_ptr<SMArray> val_holder;
-        std::unique_ptr<SMArray<std::int64_t>> idx_holder;
+        std::unique_ptr<Index> idx_holder;
         std::vector<std::int64_t> si_used(si);
         if (values && values->data.storage() == data.storage()) {
             val_holder.reset(new SMArray(values->contiguous()));
@@ -1590,7 +1546,7 @@ private:
         }
         if constexpr (std::is_same_v<T, std::int64_t>) {
             if (idx.data.storage() == data.storage()) {
-                idx_holder.reset(new SMArray<std::int64_t>(idx.contiguous()));
+                idx_holder.reset(new Index(idx.contiguous()));
                 for (std::size_t d = 0; d < nd; ++d)  // the copy is dense: a line (1-D ids, a flattened idx) has stride 1
                     if (si_used[d]) si_used[d] = idx.shape().size() == nd ? static_cast<std::int64_t>(idx_holder->strides()[d]) : 1;
             }
@@ -1598,33 +1554,26 @@ private:
         const T *vp = values->device_data();  // pending chains that produce the operands run here
         const std::int64_t *ip = idx_holder ? idx_holder->device_data() : idx.device_data();
         const auto out_shape = hip::to_i64(_shape);
-        hip::DeviceBuffer flag;  // one word from the pool, only when someone will read it
-        if (mode == index_mode::checked) flag = hip::DeviceBuffer(sizeof(std::int64_t));
+        const detail::DeviceWord<> flag(mode == index_mode::checked);  // only when someone will read it
         hip::check(smhip_scatter_axis(kind, static_cast<int>(mode), unique ? SMHIP_SCATTER_UNIQUE : 0, hip::dtype_of<T>::id,
                                       data.storage()->dev_rw() + data.offset(), out_shape.data(), static_cast<int>(nd), axis, ip, si_used.data(), vp, sv.data(),
-                                      walk[axis], flag.template as<std::int64_t>()));
+                                      walk[axis], flag.ptr()));
         ++detail::tls_fusion_stats.scatters;
-        if (mode == index_mode::checked) {
-            std::int64_t bad = 0;
-            hip::check(smhip_download(&bad, flag.get(), sizeof bad));  // waits for the stream
-            if (bad)
-                throw std::out_of_range("simpleMath/MI355X: scatter: an index is out of bounds for an axis of " + std::to_string(_shape[axis]) +
-                                        " elements (the valid entries have been applied)");
-        }
+        if (flag && flag.read())
+            throw std::out_of_range("simpleMath/MI355X: scatter: an index is out of bounds for an axis of " + std::to_string(_shape[axis]) +
+                                    " elements (the valid entries have been applied)");
         return *this;
     }
 
     // counts of this array's values between `edges` (1-D, bins + 1 of them); flags / lo / hi as smhip_histogram takes them.
-    SMArray<std::int64_t> count_between(const SMArray &edges, int flags, double lo, double hi) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "histogram: f32, f64, i32 and i64");
+    Index count_between(const SMArray &edges, int flags, double lo, double hi) const {
+        static_assert(detail::four_types_v<T>, "histogram: f32, f64, i32 and i64");
         hip::DeviceGuard on(common_device(*this, edges));
-        std::unique_ptr<SMArray> holder;
-        const T *table = edges.dense_device(holder);
-        const T *in = device_data();  // a pending chain that produces the operand runs here
+        const AbiView table = edges.flat();
+        const AbiView in = along_axis(0);  // a pending chain that produces the operand runs here
         const std::size_t bins = edges.totalSize - 1;
-        SMArray<std::int64_t> out = SMArray<std::int64_t>::device_empty(std::vector<std::size_t>{bins});
-        const auto sh = hip::to_i64(_shape), st = hip::to_i64(_strides);
-        hip::check(smhip_histogram(flags, hip::dtype_of<T>::id, in, sh.data(), st.data(), static_cast<int>(sh.size()), table, static_cast<std::int64_t>(bins), lo, hi,
+        Index out = Index::device_empty(std::vector<std::size_t>{bins});
+        hip::check(smhip_histogram(flags, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), table.ptr, static_cast<std::int64_t>(bins), lo, hi,
                                    out.device_data_mut()));
         ++detail::tls_fusion_stats.counts;
         return out;
@@ -1632,7 +1581,7 @@ private:
 
     // ---- where: `target` (dense) is both b and the result when given (assign_where), else the result goes to `out`
     static void run_where(const Cond<T> &c, const SMArray *a, T sa, const SMArray *b, T sb, const std::vector<std::size_t> &shape, SMArray *target, T *out) {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "where / assign_where: f32, f64, i32 and i64");
+        static_assert(detail::four_types_v<T>, "where / assign_where: f32, f64, i32 and i64");
         int device = c.right() ? common_device(c.left(), *c.right()) : c.left().device();
         if (a) device = common_device(c.left(), *a);
         if (b) device = common_device(c.left(), *b);
@@ -1660,21 +1609,20 @@ private:
     // The runs of the flattening (sort_first: of its stable ascending sort): count, wait, allocate exactly, emit.  A result that is not
     // wanted comes back with shape {0}.
     UniqueAll<T> runs_of(bool sort_first, bool equal_nan, bool want_index, bool want_inverse, bool want_counts) const {
-        static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "unique / unique_consecutive: f32, f64, i32 and i64");
-        using Index = SMArray<std::int64_t>;
+        static_assert(detail::four_types_v<T>, "unique / unique_consecutive: f32, f64, i32 and i64");
         const auto none = [] { return std::vector<std::size_t>{0}; };
         if (totalSize == 0) return UniqueAll<T>{device_empty(none()), Index::device_empty(none()), Index::device_empty(none()), Index::device_empty(none())};
         hip::DeviceGuard on(device());
-        std::unique_ptr<SMArray> holder;
-        const T *in = dense_device(holder);  // a pending chain that produces this operand runs here
-        const std::int64_t n = static_cast<std::int64_t>(totalSize), one = 1;
+        const AbiView flattened = flat();  // a pending chain that produces this operand runs here
+        const T *in = flattened.ptr;
+        const std::int64_t n = static_cast<std::int64_t>(totalSize);
         const int flags = equal_nan ? 0 : SMHIP_RUNS_NAN_DISTINCT;
         const bool positions = sort_first && (want_index || want_inverse);
         SMArray sorted = device_empty(std::vector<std::size_t>{sort_first ? totalSize : 0});
         Index order = Index::device_empty(std::vector<std::size_t>{positions ? totalSize : 0});
         const std::int64_t *ord = nullptr;
         if (sort_first) {
-            hip::check(smhip_sort_axis(SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, &n, &one, 1, 0, sorted.device_data_mut(),
+            hip::check(smhip_sort_axis(SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in, flattened.shape.data(), flattened.strides.data(), 1, 0, sorted.device_data_mut(),
                                        positions ? order.device_data_mut() : nullptr));
             ++detail::tls_fusion_stats.sorts;
             in = sorted.device_data();
@@ -1682,10 +1630,10 @@ private:
         }
         std::int64_t total = 0;
         {
-            hip::DeviceBuffer word(sizeof(std::int64_t));
-            hip::check(smhip_runs_count(flags, hip::dtype_of<T>::id, in, n, word.template as<std::int64_t>()));
+            const detail::DeviceWord<> word;
+            hip::check(smhip_runs_count(flags, hip::dtype_of<T>::id, in, n, word.ptr()));
             ++detail::tls_fusion_stats.uniques;
-            hip::check(smhip_download(&total, word.get(), sizeof total));  // waits for the stream
+            total = word.read();  // waits for the stream
         }
         const std::size_t runs = static_cast<std::size_t>(total);
         UniqueAll<T> r{device_empty(std::vector<std::size_t>{runs}), Index::device_empty(std::vector<std::size_t>{want_index ? runs : 0}),
@@ -1694,13 +1642,6 @@ private:
                               want_counts ? r.counts.device_data_mut() : nullptr, want_inverse ? r.inverse.device_data_mut() : nullptr, total, nullptr));
         ++detail::tls_fusion_stats.uniques;
         return r;
-    }
-
-    // Device pointer to a dense version of this array (itself when already dense).
-    const T *dense_device(std::unique_ptr<SMArray> &holder) const {
-        if (is_dense()) return device_data();
-        holder.reset(new SMArray(contiguous()));
-        return holder->device_data();
     }
 
     // arr(i, SLICE(a, b), ...): INDEX entries drop their axis, Slice entries keep a sub-range;
@@ -1898,7 +1839,7 @@ struct UniqueAll {
 // bool: `if (a > b)` does not compile.
 template <typename T>
 struct Cond {
-    static_assert(hip::dtype_of<T>::id >= 0 && hip::dtype_of<T>::id <= SMHIP_I64, "a condition compares float, double, int or std::int64_t arrays");
+    static_assert(detail::four_types_v<T>, "a condition compares float, double, int or std::int64_t arrays");
     Cond(const SMArray<T> &nonzero) : x_(nonzero.alias()) {}  // implicit: an array where a condition is expected stands for "nonzero"
     Cond(const SMArray<T> &x, smhip_cmp cmp, const SMArray<T> &y) : x_(x.alias()), y_(new SMArray<T>(y.alias())), cmp_(cmp) {}
     Cond(const SMArray<T> &x, smhip_cmp cmp, T scalar) : x_(x.alias()), cmp_(cmp), scalar_(scalar) {}
@@ -1933,12 +1874,10 @@ struct Cond {
         // np.count_nonzero: one word from the pool, downloaded -- WAITS FOR THE STREAM.
         std::int64_t count() const {
             if (empty) return 0;
-            hip::DeviceBuffer word(sizeof(std::int64_t));
-            hip::check(smhip_select_count(cmp, hip::dtype_of<T>::id, x, sx.data(), y, sy.data(), &scalar, shape.data(), ndim(), word.template as<std::int64_t>()));
+            const detail::DeviceWord<> word;
+            hip::check(smhip_select_count(cmp, hip::dtype_of<T>::id, x, sx.data(), y, sy.data(), &scalar, shape.data(), ndim(), word.ptr()));
             ++detail::tls_fusion_stats.selects;
-            std::int64_t n = 0;
-            hip::check(smhip_download(&n, word.get(), sizeof n));
-            return n;
+            return word.read();
         }
         bool empty = false;
     };

@@ -183,12 +183,10 @@ double expr_sum(const char *expression, std::initializer_list<T> scalars, const 
             ptrs[k] = dense.back().device_data();
         }
     }
-    hip::DeviceBuffer result(sizeof(double));
+    const detail::DeviceWord<double> result;
     hip::check(smhip_fused_expr_sum_async(expression, hip::dtype_of<T>::id, ptrs, n, scalars.size() ? scalars.begin() : nullptr,
-                                          static_cast<int>(scalars.size()), nullptr, first.totalSize, result.template as<double>()));
-    double total = 0;
-    hip::check(smhip_download(&total, result.get(), sizeof total));
-    return total;
+                                          static_cast<int>(scalars.size()), nullptr, first.totalSize, result.ptr()));
+    return result.read();
 }
 template <typename T, typename... Rest>
 double expr_sum(const char *expression, const SMArray<T> &first, const Rest &...rest) {

@@ -1,8 +1,9 @@
 // axis_plan.h -- the host-side planner toolbox of the axis families: reduce_axis.hip (sum, mean, max, min), scan_axis.hip
-// (cumulative scans), argreduce_axis.hip (argmax / argmin), sort_axis.hip and take_axis.hip.  Each rule they share is written here once:
+// (cumulative scans), argreduce_axis.hip (argmax / argmin), sort_axis.hip, take_axis.hip, scatter_axis.hip and count.hip.  Each rule
+// they share is written here once (the index-mode rules of take, scatter and bincount: index_mode.hip.h):
 //   * the merging of a view's axes and the canonical walk out[o, i] = f_r a[o*so + r*sr + i*si] it may come to (Canon, ROW / COLUMN);
-//   * lanes per short row (segment_lanes) and the cutting of R into chunks when a launch would have too few lanes (split_row,
-//     split_column);
+//   * lanes per short row (segment_lanes; segment_for where whole rows are copied) and the cutting of R into chunks when a launch
+//     would have too few lanes (split_row, split_column);
 //   * the capped grid (GridCap), the argument checks every entry point makes, the pooled dense copy of a view (Pooled);
 //   * vec_width, ceil_div, dense strides, and the constants and the OutMap the families' kernels are written against.
 // Header-only; everything but OutMap and the constants is host code.
@@ -104,6 +105,8 @@ inline Walk canonical(const Ax *ax, int n, Canon *c) {
 // a row of at most 64 loads gets a segment of 4, 16 or 64 lanes.  0: a longer row.
 inline int64_t row_loads(int64_t R, int64_t W) { return R / W + R % W; }
 inline int segment_lanes(int64_t loads) { return loads <= 4 ? 4 : loads <= 16 ? 16 : loads <= 64 ? 64 : 0; }
+// Rows copied whole (take, scatter): the 8, 16, 32 or 64 lanes of a wave that share a row of `per_row` lane steps.
+inline int segment_for(int64_t per_row) { return per_row <= 8 ? 8 : per_row <= 16 ? 16 : per_row <= 32 ? 32 : 64; }
 
 // Cutting R into C chunks of CL when a launch of `lanes` lanes falls short of kTargetLanes: as many chunks as make up for it,
 // none shorter than `least`, CL a multiple of `unit`; and, whatever the lanes, none longer than `max_chunk` (0: no limit).

@@ -5,8 +5,8 @@
 // terms; integer addition commutes and associates, so whatever order the increments arrive in, the counts are the same bits on every
 // run, stream and grid.  The atomics here are plain C++ atomicAdd on 32-bit words in LDS and on the 64-bit words of the result.
 //
-// NO ADDRESS OUTSIDE THE RESULT IS EVER FORMED.  An id goes through pick() (take_axis.hip's, repeated here because that one is private
-// to its file) and is a position in [0, nbins - 1] BEFORE it is used as an address; under CHECKED an id outside [-nbins, nbins) is
+// NO ADDRESS OUTSIDE THE RESULT IS EVER FORMED.  An id goes through pick() (index_mode.hip.h, shared with take_axis.hip and
+// scatter_axis.hip) and is a position in [0, nbins - 1] BEFORE it is used as an address; under CHECKED an id outside [-nbins, nbins) is
 // dropped and any lane that meets one stores the constant 1 to *bad_out.  A value's bin comes from a search that cannot leave
 // [0, E], and everything outside [0, bins - 1] is not counted.
 //
@@ -37,6 +37,7 @@
 
 #include "abi_args.h"
 #include "axis_plan.h"
+#include "index_mode.hip.h"
 #include "internal.h"
 
 namespace smhip {
@@ -55,21 +56,6 @@ constexpr int kFinishBins = 16, kFinishRows = 16;   // the finishing launch: a w
 
 template <typename T> struct alignas(16) Vec16 { T v[16 / sizeof(T)]; };
 struct alignas(16) I64x2 { int64_t v[2]; };
-
-// The position that id `i` names, in [0, R - 1] whatever `i` is.  R >= 1.  (take_axis.hip's pick.)
-template <int Mode> __device__ __forceinline__ int64_t pick(int64_t i, int64_t R, bool &bad) {
-    if constexpr (Mode == SMHIP_INDEX_WRAP) {
-        if ((uint64_t)i < (uint64_t)R) return i;  // the common case, without the 64-bit division
-        const int64_t m = i % R;                    // |m| < R; INT64_MIN % R is defined (R != -1)
-        return m < 0 ? m + R : m;
-    } else {
-        if constexpr (Mode == SMHIP_INDEX_CHECKED)
-            if (i < 0) i += R;  // cannot overflow: i < 0 < R
-        const int64_t c = i < 0 ? 0 : i >= R ? R - 1 : i;
-        if constexpr (Mode == SMHIP_INDEX_CHECKED) bad |= c != i;
-        return c;
-    }
-}
 
 // sort_axis.hip's ascending order: a number before a larger number and before every NaN.
 template <typename T> __device__ __forceinline__ bool before(T a, T b) {
@@ -361,12 +347,7 @@ template <typename B> int run_count(const B &b, const void *x, const Plan &p, in
 }
 
 template <typename I> int run_bincount(int mode, const void *ids, const Plan &p, int64_t *counts, int64_t *bad, hipStream_t s) {
-    switch (mode) {
-        case SMHIP_INDEX_CHECKED: return run_count(IdBinner<I, SMHIP_INDEX_CHECKED>{p.bins}, ids, p, counts, bad, s);
-        case SMHIP_INDEX_CLIP: return run_count(IdBinner<I, SMHIP_INDEX_CLIP>{p.bins}, ids, p, counts, bad, s);
-        case SMHIP_INDEX_WRAP: return run_count(IdBinner<I, SMHIP_INDEX_WRAP>{p.bins}, ids, p, counts, bad, s);
-    }
-    return fail(SMHIP_ERR_INVALID, "bincount: bad mode %d", mode);
+    return with_index_mode("bincount", mode, [&](auto m) { return run_count(IdBinner<I, decltype(m)::value>{p.bins}, ids, p, counts, bad, s); });
 }
 
 template <typename T> int run_histogram(bool uniform, const void *x, const void *edges, double lo, double hi, const Plan &p, int64_t *counts, hipStream_t s) {
@@ -553,7 +534,7 @@ int smhip_searchsorted(int side, int dtype, const void *edges, int64_t n_edges, 
 
 int smhip_bincount(int mode, int ids_dtype, const void *ids, const int64_t *shape, const int64_t *strides, int ndim, int64_t nbins, int64_t *counts,
                    int64_t *bad_out) {
-    if (mode != SMHIP_INDEX_CHECKED && mode != SMHIP_INDEX_CLIP && mode != SMHIP_INDEX_WRAP) return fail(SMHIP_ERR_INVALID, "bincount: bad mode %d", mode);
+    if (int rc = check_index_mode("bincount", mode)) return rc;
     if (int rc = count_check("bincount", SMHIP_COUNT_BINCOUNT, 0, ids_dtype, shape, strides, ndim, nbins)) return rc;
     const int64_t n = element_count(shape, ndim);
     if (n == 0 && nbins == 0) return SMHIP_OK;

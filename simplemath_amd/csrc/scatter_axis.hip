@@ -8,7 +8,7 @@
 // unique, the same on every run, stream and grid.  There are NO ATOMICS in this file and no two lanes ever write one address
 // (the constant-1 flag store apart): the design is an inverted index whose lists stand in a fixed order.
 //
-// NO ADDRESS OUTSIDE `out` IS EVER FORMED.  pick() (take_axis.hip's, repeated here because that one is private to its file)
+// NO ADDRESS OUTSIDE `out` IS EVER FORMED.  pick() (index_mode.hip.h, shared with take_axis.hip and count.hip)
 // turns the 64-bit index into a position in [0, R - 1] BEFORE anything is multiplied by a stride; under CHECKED an index outside
 // [-R, R) is dropped -- it writes and adds nothing -- and any lane that meets one stores the constant 1 to *bad_out.
 //
@@ -40,6 +40,7 @@
 
 #include "abi_args.h"
 #include "axis_plan.h"
+#include "index_mode.hip.h"
 #include "internal.h"
 
 namespace smhip {
@@ -49,21 +50,6 @@ using namespace axis_plan;  // kBlock, Ax, GridCap, Pooled and the planner's rul
 
 constexpr int kRowsInFlightPerLane = 4;  // ROWS: rows a lane has loads outstanding for
 constexpr int64_t kMaxSorted = (int64_t)1 << 31;  // the sort's limit on an axis
-
-// The position along the axis that index `i` names, in [0, R - 1] whatever `i` is.  R >= 1.  (take_axis.hip's pick.)
-template <int Mode> __device__ __forceinline__ int64_t pick(int64_t i, int64_t R, bool &bad) {
-    if constexpr (Mode == SMHIP_INDEX_WRAP) {
-        if ((uint64_t)i < (uint64_t)R) return i;  // the common case, without the 64-bit division
-        const int64_t m = i % R;                    // |m| < R; INT64_MIN % R is defined (R != -1)
-        return m < 0 ? m + R : m;
-    } else {
-        if constexpr (Mode == SMHIP_INDEX_CHECKED)
-            if (i < 0) i += R;  // cannot overflow: i < 0 < R
-        const int64_t c = i < 0 ? 0 : i >= R ? R - 1 : i;
-        if constexpr (Mode == SMHIP_INDEX_CHECKED) bad |= c != i;
-        return c;
-    }
-}
 
 // q / d and the remainder, through 32 bits when both fit.
 __device__ __forceinline__ int64_t div_small(int64_t q, int64_t d, int64_t *rem) {
@@ -109,7 +95,7 @@ __global__ __launch_bounds__(kBlock) void scatter_direct_kernel(T *__restrict__ 
         if constexpr (Add) *dst = (T)((A)*dst + (A)v);
         else *dst = v;
     }
-    if (Mode == SMHIP_INDEX_CHECKED && bad && bad_out) *bad_out = 1;
+    report_bad<Mode>(bad, bad_out);
 }
 
 // ------------------------------------------------------------------------------------------------------ ROWS
@@ -173,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void scatter_rows_kernel(T *__restrict__ ou
         for (int k = 0; k < F; ++k)
             if (src[k]) *reinterpret_cast<V *>(dst[k]) = v[k];
     }
-    if (Mode == SMHIP_INDEX_CHECKED && bad && bad_out) *bad_out = 1;
+    report_bad<Mode>(bad, bad_out);
 }
 
 // ------------------------------------------------------------------------------------------------------ normalise
@@ -195,7 +181,7 @@ __global__ __launch_bounds__(kBlock) void scatter_normalise_kernel(const int64_t
         bad |= b;
         keys[e] = b ? g.R : p;
     }
-    if (Mode == SMHIP_INDEX_CHECKED && bad && bad_out) *bad_out = 1;
+    report_bad<Mode>(bad, bad_out);
 }
 
 // ------------------------------------------------------------------------------------------------------ SORTED
@@ -360,14 +346,11 @@ void make_plan(int flags, int dtype, const int64_t *out_shape, int ndim, int axi
 // ------------------------------------------------------------------------------------------------------ launching
 const GridCap &grid_cap() { static const GridCap g(getenv("SMHIP_SCATTER_GRID_CAP")); return g; }  // the cap of every launch here, read once
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-int segment_for(int64_t per_row) { return per_row <= 8 ? 8 : per_row <= 16 ? 16 : per_row <= 32 ? 32 : 64; }
-
 template <typename T, bool Add, int Mode>
 int run_unique(const Plan &p, T *out, const int64_t *idx, const T *val, int64_t *bad, hipStream_t s) {
     constexpr int W = 16 / (int)sizeof(T);
     if (p.route == SMHIP_SCATTER_ROUTE_ROWS) {
-        const bool vec = aligned16(out) && aligned16(val) && p.I % W == 0 && p.svo % W == 0 && p.svj % W == 0 && p.oso % W == 0 && p.sor % W == 0;
+        const bool vec = !misaligned(out, 16) && !misaligned(val, 16) && p.I % W == 0 && p.svo % W == 0 && p.svj % W == 0 && p.oso % W == 0 && p.sor % W == 0;
         const int64_t per_row = ceil_div(p.I, vec ? W : 1);  // lane steps a row takes
         const RowsArgs g{p.O, p.J, p.I, p.R, p.sio, p.sij, p.svo, p.svj, p.oso, p.sor, segment_for(per_row)};
         const int64_t piece = (int64_t)g.seg * (vec ? W : 1);
@@ -399,18 +382,12 @@ int run_sorted(const Plan &p, int mode, T *out, const int64_t *idx, const T *val
     void *raw;
     if (int rc = pool.take((size_t)p.sorted * 2 * sizeof(int64_t), &raw)) return rc;
     int64_t *keys = static_cast<int64_t *>(raw), *order = keys + p.sorted;
-    int rc = SMHIP_OK;
-    switch (mode) {
-        case SMHIP_INDEX_CHECKED: rc = run_normalise<SMHIP_INDEX_CHECKED>(p, idx, keys, bad, s); break;
-        case SMHIP_INDEX_CLIP: rc = run_normalise<SMHIP_INDEX_CLIP>(p, idx, keys, bad, s); break;
-        default: rc = run_normalise<SMHIP_INDEX_WRAP>(p, idx, keys, bad, s); break;
-    }
-    if (rc) return rc;
+    if (int rc = with_index_mode("scatter_axis", mode, [&](auto m) { return run_normalise<decltype(m)::value>(p, idx, keys, bad, s); })) return rc;
     const int64_t shape2[2] = {p.Op * p.Ip, p.J}, strides2[2] = {p.J, 1};
     if (int rc2 = launch_sort_axis(SMHIP_SORT_ASCENDING, SMHIP_I64, keys, shape2, strides2, 2, 1, keys, order, s)) return rc2;  // the keys in place
     SortedArgs g{p.O, p.J, p.I, p.R, p.Op > 1 ? p.Ip : 0, p.Ip > 1 ? 1 : 0, p.svo, p.svj, p.svi, p.oso, p.sor, p.osi, 64};
     if (p.route == SMHIP_SCATTER_ROUTE_SORTED_ROWS) {
-        const bool vec = aligned16(out) && aligned16(val) && p.I % W == 0 && p.svo % W == 0 && p.svj % W == 0 && p.oso % W == 0 && p.sor % W == 0;
+        const bool vec = !misaligned(out, 16) && !misaligned(val, 16) && p.I % W == 0 && p.svo % W == 0 && p.svj % W == 0 && p.oso % W == 0 && p.sor % W == 0;
         g.seg = segment_for(ceil_div(p.I, vec ? W : 1));
         const int64_t piece = (int64_t)g.seg * (vec ? W : 1);
         const int64_t tasks = ceil_div(p.O * p.J, (int64_t)(64 / g.seg)) * ceil_div(p.I, piece);
@@ -430,19 +407,14 @@ int run_plan(const Plan &p, int mode, void *out, const int64_t *idx, const void 
     T *po = static_cast<T *>(out);
     const T *pv = static_cast<const T *>(val);
     if (!p.unique) return run_sorted<T, Add>(p, mode, po, idx, pv, bad, s);
-    switch (mode) {
-        case SMHIP_INDEX_CHECKED: return run_unique<T, Add, SMHIP_INDEX_CHECKED>(p, po, idx, pv, bad, s);
-        case SMHIP_INDEX_CLIP: return run_unique<T, Add, SMHIP_INDEX_CLIP>(p, po, idx, pv, bad, s);
-        case SMHIP_INDEX_WRAP: return run_unique<T, Add, SMHIP_INDEX_WRAP>(p, po, idx, pv, bad, s);
-    }
-    return fail(SMHIP_ERR_INVALID, "scatter_axis: bad mode %d", mode);
+    return with_index_mode("scatter_axis", mode, [&](auto m) { return run_unique<T, Add, decltype(m)::value>(p, po, idx, pv, bad, s); });
 }
 
 // Validation: everything that can be said without a device or a pointer.
 int scatter_axis_check(const char *who, int kind, int mode, int flags, int dtype, const int64_t *out_shape, int ndim, int axis, const int64_t *idx_strides,
                        const int64_t *val_strides, int64_t n_entries) {
     if (kind != SMHIP_SCATTER_PUT && kind != SMHIP_SCATTER_ADD) return fail(SMHIP_ERR_INVALID, "%s: bad kind %d", who, kind);
-    if (mode != SMHIP_INDEX_CHECKED && mode != SMHIP_INDEX_CLIP && mode != SMHIP_INDEX_WRAP) return fail(SMHIP_ERR_INVALID, "%s: bad mode %d", who, mode);
+    if (int rc = check_index_mode(who, mode)) return rc;
     if (flags & ~SMHIP_SCATTER_UNIQUE) return fail(SMHIP_ERR_INVALID, "%s: unknown flag bits 0x%x", who, flags);
     if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
     if (int rc = check_axis(who, axis, ndim)) return rc;

@@ -7,7 +7,7 @@
 // f32 / i32 and f64 / i64 share their code, and the result is unique whatever the route, the grid or the stream.
 //
 // NO ADDRESS OUTSIDE `a` IS EVER FORMED.  Every kernel turns the 64-bit index it read into a position p in [0, R - 1] with pick()
-// BEFORE anything is multiplied by a stride or added to a pointer: CHECKED and CLIP clamp, WRAP takes the non-negative remainder
+// (index_mode.hip.h, shared with scatter_axis.hip and count.hip) BEFORE anything is multiplied by a stride or added to a pointer: CHECKED and CLIP clamp, WRAP takes the non-negative remainder
 // (R >= 1 is checked on the host, so the range is never empty; INT64_MIN and INT64_MAX go through the same 64-bit arithmetic,
 // nothing is narrowed to 32 bits first).  The offset o*sao + p*sar + i*sai is then one that the host's span check covered.
 // A bad index under CHECKED is reported, not followed: any lane that meets one writes the constant 1 to *bad_out with a plain
@@ -35,6 +35,7 @@
 
 #include "abi_args.h"
 #include "axis_plan.h"
+#include "index_mode.hip.h"
 #include "internal.h"
 
 namespace smhip {
@@ -46,21 +47,6 @@ constexpr int kLineBytes = 32 << 10;   // LINE: the longest line staged in LDS (
 constexpr int kRowsInFlightPerLane = 4;  // ROWS: rows a lane has loads outstanding for
 constexpr int kDefaultLineRatio = 2;   // c: LINE when J >= R / c.  profiles/take_rates.txt: on (131072, 1000) f32 DIRECT wins 1.7x at J = R / 20 and
                                        // LINE 1.08x at J = R; the straight line between the two crosses near J = 0.6 R
-
-// The position along the gathered axis that index `i` names, in [0, R - 1] whatever `i` is.  R >= 1.
-template <int Mode> __device__ __forceinline__ int64_t pick(int64_t i, int64_t R, bool &bad) {
-    if constexpr (Mode == SMHIP_INDEX_WRAP) {
-        if ((uint64_t)i < (uint64_t)R) return i;  // the common case, without the 64-bit division
-        const int64_t m = i % R;                    // |m| < R; INT64_MIN % R is defined (R != -1)
-        return m < 0 ? m + R : m;
-    } else {
-        if constexpr (Mode == SMHIP_INDEX_CHECKED)
-            if (i < 0) i += R;  // cannot overflow: i < 0 < R
-        const int64_t c = i < 0 ? 0 : i >= R ? R - 1 : i;
-        if constexpr (Mode == SMHIP_INDEX_CHECKED) bad |= c != i;
-        return c;
-    }
-}
 
 // q / d and the remainder, through 32 bits when both fit.
 __device__ __forceinline__ int64_t div_small(int64_t q, int64_t d, int64_t *rem) {
@@ -119,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void take_line_kernel(const U *__restrict__
         }
         __syncthreads();  // the next task reuses the lines
     }
-    if (Mode == SMHIP_INDEX_CHECKED && bad && bad_out) *bad_out = 1;
+    report_bad<Mode>(bad, bad_out);
 }
 
 // ------------------------------------------------------------------------------------------------------ ROWS
@@ -166,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void take_rows_kernel(const U *__restrict__
         for (int k = 0; k < F; ++k)
             if (src[k]) *reinterpret_cast<V *>(dst[k]) = v[k];
     }
-    if (Mode == SMHIP_INDEX_CHECKED && bad && bad_out) *bad_out = 1;
+    report_bad<Mode>(bad, bad_out);
 }
 
 // ------------------------------------------------------------------------------------------------------ DIRECT
@@ -190,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void take_direct_kernel(const U *__restrict
         const int64_t p = pick<Mode>(idx[at], g.R, bad);
         out[e] = a[c[0] * g.sa[0] + c[1] * g.sa[1] + c[2] * g.sa[2] + p * g.sar];
     }
-    if (Mode == SMHIP_INDEX_CHECKED && bad && bad_out) *bad_out = 1;
+    report_bad<Mode>(bad, bad_out);
 }
 
 // ------------------------------------------------------------------------------------------------------ the planner
@@ -288,8 +274,6 @@ void make_plan(int dtype, const int64_t *a_strides, int64_t a_extent, const int6
 // ------------------------------------------------------------------------------------------------------ launching
 const GridCap &grid_cap() { static const GridCap g(getenv("SMHIP_TAKE_GRID_CAP")); return g; }  // the cap of every launch here, read once
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <typename U, int Mode>
 int run_mode(const Plan &p, const U *a, const int64_t *idx, U *out, int64_t *bad, hipStream_t s) {
     constexpr int W = 16 / (int)sizeof(U);
@@ -299,9 +283,9 @@ int run_mode(const Plan &p, const U *a, const int64_t *idx, U *out, int64_t *bad
                            idx, out, g, bad);
         SMHIP_LAUNCH_CHECK("take_axis line");
     } else if (p.route == SMHIP_TAKE_ROUTE_ROWS) {
-        const bool vec = aligned16(a) && aligned16(out) && p.I % W == 0 && p.sar % W == 0 && p.sao % W == 0 && p.oso % W == 0 && p.osj % W == 0;
+        const bool vec = !misaligned(a, 16) && !misaligned(out, 16) && p.I % W == 0 && p.sar % W == 0 && p.sao % W == 0 && p.oso % W == 0 && p.osj % W == 0;
         const int64_t per_row = ceil_div(p.I, vec ? W : 1);  // lane steps a row takes
-        RowsArgs g{p.O, p.J, p.I, p.R, p.sao, p.sar, p.sio, p.sij, p.oso, p.osj, per_row <= 8 ? 8 : per_row <= 16 ? 16 : per_row <= 32 ? 32 : 64};
+        RowsArgs g{p.O, p.J, p.I, p.R, p.sao, p.sar, p.sio, p.sij, p.oso, p.osj, segment_for(per_row)};
         const int64_t piece = (int64_t)g.seg * (vec ? W : 1);
         const int64_t tasks = ceil_div(p.O * p.J, (int64_t)(64 / g.seg) * kRowsInFlightPerLane) * ceil_div(p.I, piece);
         const unsigned blocks = grid_cap().blocks_for(tasks);
@@ -325,18 +309,13 @@ template <typename U>
 int run_plan(const Plan &p, int mode, const void *a, const int64_t *idx, void *out, int64_t *bad, hipStream_t s) {
     const U *pa = static_cast<const U *>(a);
     U *po = static_cast<U *>(out);
-    switch (mode) {
-        case SMHIP_INDEX_CHECKED: return run_mode<U, SMHIP_INDEX_CHECKED>(p, pa, idx, po, bad, s);
-        case SMHIP_INDEX_CLIP: return run_mode<U, SMHIP_INDEX_CLIP>(p, pa, idx, po, bad, s);
-        case SMHIP_INDEX_WRAP: return run_mode<U, SMHIP_INDEX_WRAP>(p, pa, idx, po, bad, s);
-    }
-    return fail(SMHIP_ERR_INVALID, "take_axis: bad mode %d", mode);
+    return with_index_mode("take_axis", mode, [&](auto m) { return run_mode<U, decltype(m)::value>(p, pa, idx, po, bad, s); });
 }
 
 // Validation: everything that can be said without a device or a pointer.
 int take_axis_check(const char *who, int mode, int dtype, const int64_t *a_strides, int64_t a_extent, const int64_t *idx_strides, const int64_t *out_shape,
                     int ndim, int axis) {
-    if (mode != SMHIP_INDEX_CHECKED && mode != SMHIP_INDEX_CLIP && mode != SMHIP_INDEX_WRAP) return fail(SMHIP_ERR_INVALID, "%s: bad mode %d", who, mode);
+    if (int rc = check_index_mode(who, mode)) return rc;
     if (int rc = check_dtype_ndim(who, dtype, ndim)) return rc;
     if (int rc = check_axis(who, axis, ndim)) return rc;
     if (int rc = check_extents(who, out_shape, a_strides, ndim)) return rc;

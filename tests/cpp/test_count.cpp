@@ -266,6 +266,14 @@ static void test_bincount() {
             ++of_view[static_cast<std::size_t>(id < 0 ? id + 20000 : id)];
         }
     CHECK(differences(sm::bincount(grid(SLICE_ALL, SLICE(0, 150)), 20000), of_view) == 0);
+    // four ids, one of them out of range: checked throws (the counts go with the exception), and the next calls on this thread work --
+    // the same ids with the bad one clipped, then checked again without it
+    auto four = from_host(std::vector<I>{I(1), I(4), I(-1), I(1)}, {4});
+    const auto before = sm::fusion_stats();
+    CHECK(throws_out_of_range([&] { four.bincount(4); }));
+    CHECK(sm::fusion_stats().counts - before.counts == 1);
+    CHECK(differences(four.bincount(4, sm::index_mode::clip), std::vector<I64>{1, 2, 0, 1}) == 0);
+    CHECK(differences(four(SLICE(2, 4)).bincount(4), std::vector<I64>{0, 1, 0, 1}) == 0);
 }
 
 static void test_chains_and_counter() {

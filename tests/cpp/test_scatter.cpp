@@ -398,12 +398,64 @@ static void test_readme_snippets() {
     CHECK(bad == 0);
 }
 
+// The flat forms on operands that are not dense -- a transposed 3 x 5 target, a transposed index array -- against the same call on
+// their contiguous copies; and one checked-mode bad index on a 1-D target of 4 elements.
+template <typename T>
+static void test_flat_views_and_small_checked() {
+    std::vector<T> h, hv;
+    std::vector<std::int64_t> hi;
+    for (bool flat_ids : {false, true}) {
+        auto a = host_array<T>({3, 5}, h);
+        auto b = from_host(h, {3, 5});
+        auto tr = a.transpose();                   // {5, 3}, not dense
+        auto dense = b.transpose().contiguous();   // the same elements, dense
+        auto idx = host_index({2, 4}, hi, -15, 15);
+        auto idx_t = host_index({4, 2}, hi, -15, 15);
+        auto v = host_array<T>({8}, hv);
+        const auto before = sm::fusion_stats();
+        if (flat_ids) {
+            tr.put_flat(from_host(std::vector<std::int64_t>(hi.begin(), hi.end()), {8}), v);
+            dense.put_flat(from_host(std::vector<std::int64_t>(hi.begin(), hi.end()), {8}), v);
+        } else {
+            tr.put_along_axis(idx, v);
+            dense.put_along_axis(idx, v);
+            tr.put_along_axis(idx_t.transpose(), T(7));  // the index array a view as well
+            dense.put_along_axis(idx_t.transpose().contiguous(), T(7));
+        }
+        CHECK(sm::fusion_stats().scatters - before.scatters == (flat_ids ? 2u : 4u));
+        std::vector<T> want(15);
+        dense.copy_dense_out(want.data());
+        CHECK(differences(tr, want) == 0);
+        // ... and a is its transpose
+        std::vector<T> back(15);
+        for (std::size_t i = 0; i < 3; ++i)
+            for (std::size_t j = 0; j < 5; ++j) back[i * 5 + j] = want[j * 3 + i];
+        CHECK(differences(a, back) == 0);
+    }
+    // checked: index 4 of 4 elements is dropped, the valid entries are applied, std::out_of_range; the next call works
+    const auto ids = from_host(std::vector<std::int64_t>{1, 4, -1}, {3});
+    const auto v = from_host(std::vector<T>{T(10), T(20), T(30)}, {3});
+    auto p = from_host(std::vector<T>{T(1), T(2), T(3), T(4)}, {4});
+    CHECK(throws_out_of_range([&] { p.put(ids, v, 0); }));
+    CHECK(differences(p, std::vector<T>{T(1), T(10), T(3), T(30)}) == 0);
+    CHECK(throws_out_of_range([&] { p.scatter_add(ids, v, 0); }));
+    CHECK(differences(p, std::vector<T>{T(1), T(20), T(3), T(60)}) == 0);
+    CHECK(throws_out_of_range([&] { p.put_flat(ids, T(5)); }));
+    CHECK(differences(p, std::vector<T>{T(1), T(5), T(3), T(5)}) == 0);
+    p.index_add(ids, v, 0, sm::index_mode::clip);
+    CHECK(differences(p, std::vector<T>{T(31), T(15), T(3), T(25)}) == 0);  // clip: 4 names the last position, -1 the first
+}
+
 int main() {
     try {
         test_forms<float>();
         test_forms<double>();
         test_forms<int>();
         test_forms<std::int64_t>();
+        test_flat_views_and_small_checked<float>();
+        test_flat_views_and_small_checked<double>();
+        test_flat_views_and_small_checked<int>();
+        test_flat_views_and_small_checked<std::int64_t>();
         test_index_modes();
         test_views_chains_and_counter();
         test_nan_payload_and_signed_zero();

@@ -173,6 +173,49 @@ static void test_forms() {
     CHECK(throws_invalid_argument([&] { (void)sm::take_flat(a, idx2); }));
 }
 
+// The flat forms with BOTH operands not dense -- a transposed 3 x 5 array, a transposed index array -- against the same call on
+// their contiguous copies; and one checked-mode bad index on a 1-D array of 4 elements.
+template <typename T>
+static void test_flat_views_and_small_checked() {
+    std::vector<T> h;
+    std::vector<std::int64_t> hi;
+    auto a = host_array<T>({3, 5}, h);
+    auto idx = host_index({4, 2}, hi, -15, 15);
+    const auto tr = a.transpose();      // {5, 3}
+    const auto ix = idx.transpose();    // {2, 4}
+    const auto dense = tr.contiguous();
+    const auto dense_ix = ix.contiguous();
+    const auto before = sm::fusion_stats();
+    const auto want = dense.take_along_axis(dense_ix);
+    const auto got = tr.take_along_axis(ix);
+    CHECK(sm::fusion_stats().takes - before.takes == 2);
+    CHECK((got.shape() == Shape{8}));
+    CHECK(std::memcmp(got.cdata(), want.cdata(), 8 * sizeof(T)) == 0);
+    std::vector<T> by_hand(8);
+    for (std::size_t k = 0; k < 8; ++k) {
+        const std::size_t at = static_cast<std::size_t>(checked_position(hi[(k % 4) * 2 + k / 4], 15));  // ix[k / 4][k % 4] = idx[k % 4][k / 4]
+        by_hand[k] = h[(at % 3) * 5 + at / 3];                                                            // tr's flattening: tr[at / 3][at % 3]
+    }
+    CHECK(differences(got, by_hand) == 0);
+    // checked: index 4 of 4 elements throws std::out_of_range; the next call on this thread works
+    auto four = host_array<T>({4}, h);
+    sm::SMArray<std::int64_t> ids(new std::int64_t[3]{1, 4, -1}, Shape{3});
+    int threw = 0;
+    try {
+        (void)four.take(ids, 0);
+    } catch (const std::out_of_range &) {
+        ++threw;
+    }
+    try {
+        (void)four.take_flat(ids);
+    } catch (const std::out_of_range &) {
+        ++threw;
+    }
+    CHECK(threw == 2);
+    CHECK(differences(four.take(ids, 0, sm::index_mode::clip), std::vector<T>{h[1], h[3], h[0]}) == 0);
+    CHECK(differences(four.take(ids(SLICE(0, 1)), 0), std::vector<T>{h[1]}) == 0);
+}
+
 static void test_index_modes() {
     std::vector<float> h;
     auto a = host_array<float>({9, 300}, h);
@@ -338,6 +381,10 @@ int main() {
         test_forms<double>();
         test_forms<int>();
         test_forms<std::int64_t>();
+        test_flat_views_and_small_checked<float>();
+        test_flat_views_and_small_checked<double>();
+        test_flat_views_and_small_checked<int>();
+        test_flat_views_and_small_checked<std::int64_t>();
         test_index_modes();
         test_views_chains_and_counter();
         test_nan_payload_and_signed_zero();
