@@ -120,6 +120,7 @@ struct FusionStats {
     unsigned long long counts = 0;              // smhip_searchsorted / smhip_bincount / smhip_histogram calls
     unsigned long long selects = 0;             // smhip_where / smhip_select_count / smhip_select calls
     unsigned long long uniques = 0;             // smhip_runs_count / smhip_runs calls: unique_* / unique_consecutive / run_lengths (a count, then the runs)
+    unsigned long long topks = 0;               // smhip_topk_axis calls: topk / topk_flat
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -846,6 +847,16 @@ public:
     SMArray sort_flat(bool descending = false) const { return sort_of(std::nullopt, descending, true, false).first; }
     SMArray<std::int64_t> argsort_flat(bool descending = false) const { return sort_of(std::nullopt, descending, false, true).second; }
 
+    // The k FIRST of that order without sorting the line: {values, positions}, bit for bit the first k along `axis` of
+    // sort_with_index(axis, largest), of this array's shape with k on `axis` (topk_flat: of the row-major flattening, shape {k}).
+    // largest = true gives NaNs, then the k largest, entry 0 where argmax points; largest = false the k smallest, NaNs last; equal
+    // elements come in rising position, and the results are always in that order.  The operand may be a view or a pending chain
+    // (evaluated first); each is ONE smhip_topk_axis call (counted in sm::fusion_stats().topks) whose results stay on the device and
+    // feed the next chain, take_along_axis or put_along_axis.  A negative axis counts from the end; an axis out of range or a k
+    // above the axis' extent throws std::invalid_argument.
+    std::pair<SMArray, SMArray<std::int64_t>> topk(std::size_t k, int axis = -1, bool largest = true) const { return topk_of(k, axis, largest); }
+    std::pair<SMArray, SMArray<std::int64_t>> topk_flat(std::size_t k, bool largest = true) const { return topk_of(k, std::nullopt, largest); }
+
     // PICKING BY POSITION along an axis (np.take_along_axis / np.take): the consumer of what argmax, argsort and sort_with_index
     // produce.  take_along_axis: `idx` is an SMArray<std::int64_t> of this array's rank whose other axes equal this array's
     // or broadcast against them; result[..., j, ...] = (*this)[..., idx[..., j, ...], ...], of the broadcast shape with idx's
@@ -1427,6 +1438,23 @@ private:
         hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(),
                                    in.ndim(), in.axis, want_values ? r.first.device_data_mut() : nullptr, want_where ? r.second.device_data_mut() : nullptr));
         ++detail::tls_fusion_stats.sorts;
+        return r;
+    }
+
+    // {the first k of the order, their positions}, of this array's shape with k on the axis (without an axis: of {k}).
+    std::pair<SMArray, Index> topk_of(std::size_t k, std::optional<int> axis, bool largest) const {
+        static_assert(detail::four_types_v<T>, "topk: f32, f64, i32 and i64");
+        if (axis) axis = detail::normal_axis<std::invalid_argument>(*axis, _shape.size(), "topk: ");
+        const std::size_t extent = axis ? _shape[*axis] : totalSize;
+        if (k > extent) throw std::invalid_argument("simpleMath/MI355X: topk: k " + std::to_string(k) + " above the axis' extent " + std::to_string(extent));
+        hip::DeviceGuard on(device());
+        const AbiView in = line(axis);  // a pending chain that produces this operand runs here
+        std::vector<std::size_t> shape = axis ? _shape : std::vector<std::size_t>{totalSize};
+        shape[in.axis] = k;
+        std::pair<SMArray, Index> r{device_empty(std::vector<std::size_t>(shape)), Index::device_empty(std::vector<std::size_t>(shape))};
+        hip::check(smhip_topk_axis(largest ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(),
+                                   in.ndim(), in.axis, static_cast<std::int64_t>(k), r.first.device_data_mut(), r.second.device_data_mut()));
+        ++detail::tls_fusion_stats.topks;
         return r;
     }
 

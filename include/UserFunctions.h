@@ -276,6 +276,13 @@ SMArray<T> sort_flat(const SMArray<T> &arr, bool descending = false) { return ar
 template <typename T>
 SMArray<std::int64_t> argsort_flat(const SMArray<T> &arr, bool descending = false) { return arr.argsort_flat(descending); }
 
+// The k first of that order without the sort: {values, positions}, the first k along `axis` of sort_with_index(arr, axis, largest),
+// bit for bit; topk_flat takes the row-major flattening, shape {k}.  Semantics as SMArray::topk (SMArray.h) and smhip_topk_axis.
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> topk(const SMArray<T> &arr, std::size_t k, int axis = -1, bool largest = true) { return arr.topk(k, axis, largest); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<std::int64_t>> topk_flat(const SMArray<T> &arr, std::size_t k, bool largest = true) { return arr.topk_flat(k, largest); }
+
 // Picking by position along an axis (np.take_along_axis / np.take): result[..., j, ...] = arr[..., idx[..., j, ...], ...].
 // take_along_axis: `idx` has arr's rank, its other axes equal to arr's or broadcastable; without an axis both are flattened.
 // take: `idx` is 1-D, the result is arr's shape with `axis` replaced by idx.size(); take_flat indexes the row-major flattening.

@@ -514,6 +514,44 @@ int smhip_sort_axis(int order, int dtype, const void *a, const int64_t *shape, c
 int smhip_sort_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
                     int *route, int *launches, int64_t *ori3, int64_t *chunk);
 
+/* ------------------------------------------------------------------ topk */
+/* The first k of the order along ONE axis, without sorting the line: values_out and index_out are, bit for bit, the first k entries
+ * along `axis` of what smhip_sort_axis(order, ...) writes.  The contract is the one above:
+ *   DESCENDING   ("the k largest") NaNs first (all NaNs tie), then the larger value first, -0.0 == +0.0;
+ *   ASCENDING    ("the k smallest") the smaller value first, NaNs last;
+ *   ties         in both, equal elements come in rising position.  Entry 0 of DESCENDING is what smhip_argreduce_axis(ARG_MAX) returns.
+ * The pairs of a line are totally ordered, so the result is unique: the same bytes on every run, stream and grid, whatever the route
+ * (the only atomics are integer counts).  The results are always in that order; there is no unsorted form.  values_out holds the
+ * operand's own bits (which zero, which NaN payload), index_out the positions along the axis as int64_t.  Both are dense row-major
+ * over `shape` with shape[axis] replaced by k, and either may be NULL, not both.
+ * `a` is any view, as for smhip_sort_axis; f32, f64, i32 and i64.  Checked before any device is touched: everything
+ * smhip_sort_axis refuses (SMHIP_ERR_INVALID: order, dtype, ndim, axis, negative extents or strides, null a / shape / strides, both
+ * outputs null, the outputs overlapping each other, an output overlapping a's span -- there is NO in-place form), k < 0 or
+ * k > shape[axis] (SMHIP_ERR_INVALID), and shape[axis] >= 2^31 (SMHIP_ERR_UNSUPPORTED).  k == shape[axis] is the sort; k == 0 or
+ * any extent of 0 is a no-op, whatever the pointers; shape[axis] == 1 copies the values and writes zeros.  Asynchronous,
+ * stream-ordered: it is ordered behind everything queued and everything later behind it; recorded tiny operators are flushed first. */
+int smhip_topk_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                    int64_t k, void *values_out_or_null, int64_t *index_out_or_null);
+/* Host only, no device touched: the route smhip_topk_axis would take.  *route = a kernel id (SMHIP_TOPK_ROUTE_*) ORed with the flags
+ * below; *launches = the kernel launches of a call that asks for both outputs; ori3 = {O, R, I} as smhip_sort_plan reports them;
+ * info3 = {L, kmax, selection levels}: L the longest line a selection holds in LDS, kmax the largest k it takes (both the same for
+ * every shape), and the selection launches of this call (1 for ROW, more with TILED, 0 otherwise).  Any output may be NULL. */
+#define SMHIP_TOPK_ROUTE_NONE 0      /* an extent or k is 0: nothing to compute */
+#define SMHIP_TOPK_ROUTE_COPYONLY 1  /* R = 1: the dense copy of a and zeros for the positions */
+#define SMHIP_TOPK_ROUTE_ROW 2       /* k <= kmax: a line (R <= L) is loaded into LDS once, its first k pairs selected by a radix select
+                                        on a monotone key, ordered by a bitonic network over k slots and written: ONE launch.  A line
+                                        of at most SMHIP_TOPK_RANKED elements is ranked by all pairs instead, whatever k is */
+#define SMHIP_TOPK_ROUTE_SORT 3      /* k > kmax, or 2k > R on a line of SMHIP_TOPK_RANKED < R <= L elements (a selection that keeps more
+                                        than half of the line): smhip_sort_axis's kernels into pooled arrays, then a strided copy of
+                                        the first k per output */
+#define SMHIP_TOPK_RANKED 128        /* the longest line that is ranked, a wave per line */
+#define SMHIP_TOPK_TILED 0x100       /* R > L: the first min(k, tile) pairs of every tile of L go to pooled candidates, and the selection
+                                        is repeated on each line's candidates until one tile is left; that launch writes the results */
+#define SMHIP_TOPK_COPY 0x200        /* staging, decided as smhip_sort_plan decides it: the operand copied so that the axis is the
+                                        unit-stride one, and / or the result rows scattered to the dense results (a launch per output) */
+int smhip_topk_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int64_t k,
+                    int *route, int *launches, int64_t *ori3, int64_t *info3);
+
 /* ------------------------------------------------ take / take_along_axis */
 /* Picking by position along ONE axis, np.take_along_axis:  out[..., j, ...] = a[..., idx[..., j, ...], ...].  np.take(a, ids,
  * axis) is the same call with the 1-D index array broadcast (stride 0) over every axis but `axis`.  The contract:

@@ -52,6 +52,10 @@ SORT_ASCENDING, SORT_DESCENDING = range(2)  # smhip_sort_order
 # smhip_sort_plan's route word: a kernel id in the low byte, flags above it
 SORT_ROUTE_NONE, SORT_ROUTE_COPYONLY, SORT_ROUTE_ROW = range(3)
 SORT_MERGE, SORT_COPY = 0x100, 0x200
+# smhip_topk_plan's route word: a kernel id in the low byte, flags above it
+TOPK_ROUTE_NONE, TOPK_ROUTE_COPYONLY, TOPK_ROUTE_ROW, TOPK_ROUTE_SORT = range(4)
+TOPK_TILED, TOPK_COPY = 0x100, 0x200
+TOPK_RANKED = 128  # SMHIP_TOPK_RANKED: the longest line that is ranked, whatever k is
 INDEX_CHECKED, INDEX_CLIP, INDEX_WRAP = range(3)  # smhip_index_mode
 INDEX_MODES = {"checked": INDEX_CHECKED, "raise": INDEX_CHECKED, "clip": INDEX_CLIP, "wrap": INDEX_WRAP}
 # smhip_take_plan's route word: a kernel id in the low byte, the flag above it
@@ -834,6 +838,55 @@ class Smhip:
         self._ck(self.c.smhip_sort_plan(C.c_int(SORT_DESCENDING if descending else SORT_ASCENDING), C.c_int(dtype), _i64(shape), _i64(strides),
                                         C.c_int(len(shape)), C.c_int(int(axis)), C.byref(route), C.byref(launches), ori, C.byref(chunk)))
         return route.value, launches.value, tuple(int(x) for x in ori), chunk.value
+
+    def topk(self, a: DeviceArray, k, axis=-1, largest=True, out: DeviceArray | None = None, index_out: DeviceArray | None = None):
+        """The first k along `axis` of sort(a, axis, descending=largest, indices=True), without the sort -> (values, indices): new
+        dense DeviceArrays of a's shape with shape[axis] replaced by k (or `out` / `index_out`, dense arrays of a's dtype / int64 with
+        as many elements, never the operand).  largest=True: NaNs, then the larger values first; largest=False: the smaller values
+        first, NaNs last; equal elements in rising position.  `a` is any view; axis=None takes the row-major flattening and gives
+        shape (k,).  ValueError for a dtype outside f32, f64, i32 and i64, k outside 0..shape[axis], or a bad out / index_out."""
+        if a.dtype not in DTYPES:
+            raise ValueError(f"topk: dtype {a.dtype} (f32, f64, i32 and i64 only)")
+        k = int(k)
+        if axis is None:
+            if not a.is_dense():  # the row-major order of a view: its dense copy
+                dense = self.empty(a.shape, a.dtype)
+                self.assign(dense, a)
+                a = dense
+            shape, strides, axis = (a.size,), (1,), 0
+        else:
+            (axis,) = self._axes(a.ndim, int(axis))
+            shape, strides = a.shape, a.strides
+        if k < 0 or k > shape[axis]:
+            raise ValueError(f"topk: k {k} outside 0..{shape[axis]}")
+        result_shape = tuple(shape[:axis]) + (k,) + tuple(shape[axis + 1:])
+        n = int(np.prod(result_shape, dtype=np.int64))
+        for given, dtype, name in ((out, a.dtype, "out"), (index_out, np.dtype(np.int64), "index_out")):
+            if given is not None and (given.dtype != dtype or given.size != n or not given.is_dense()):
+                raise ValueError(f"topk: {name} must be a dense {dtype} array of {n} elements (shape {result_shape}); "
+                                 f"got {given.dtype} {given.shape} dense={given.is_dense()}")
+        vals = out if out is not None else self.empty(result_shape, a.dtype)
+        idx = index_out if index_out is not None else self.empty(result_shape, np.int64)
+        self._ck(self.c.smhip_topk_axis(C.c_int(SORT_DESCENDING if largest else SORT_ASCENDING), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr),
+                                        _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(axis), C.c_int64(k),
+                                        C.c_void_p(vals.ptr), C.c_void_p(idx.ptr)))
+        return vals, idx
+
+    def topk_raw(self, order, dtype, a_ptr, shape, strides, axis, k, values_ptr=0, index_ptr=0, ndim=None):
+        """smhip_topk_axis with every argument as given (argument-validation tests, one output alone); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        return self.c.smhip_topk_axis(C.c_int(order), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                      _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_int(axis), C.c_int64(k),
+                                      C.c_void_p(values_ptr), C.c_void_p(index_ptr))
+
+    def topk_plan(self, dtype, shape, strides, axis, k, largest=True):
+        """smhip_topk_plan (host only): (route word, launches, (O, R, I), (L, kmax, selection levels)) for a call on shape / strides (elements)."""
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        self._ck(self.c.smhip_topk_plan(C.c_int(SORT_DESCENDING if largest else SORT_ASCENDING), C.c_int(dtype), _i64(shape), _i64(strides),
+                                        C.c_int(len(shape)), C.c_int(int(axis)), C.c_int64(int(k)), C.byref(route), C.byref(launches), ori, info))
+        return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
 
     def take_along_axis(self, a: DeviceArray, idx: DeviceArray, axis, mode="checked", out: DeviceArray | None = None):
         """np.take_along_axis(a, idx, axis): out[..., j, ...] = a[..., idx[..., j, ...], ...] -> a new dense DeviceArray (or into

@@ -1,5 +1,5 @@
 // axis_plan.h -- the host-side planner toolbox of the axis families: reduce_axis.hip (sum, mean, max, min), scan_axis.hip
-// (cumulative scans), argreduce_axis.hip (argmax / argmin), sort_axis.hip, take_axis.hip, scatter_axis.hip and count.hip.  Each rule
+// (cumulative scans), argreduce_axis.hip (argmax / argmin), sort_axis.hip, topk_axis.hip, take_axis.hip, scatter_axis.hip and count.hip.  Each rule
 // they share is written here once (the index-mode rules of take, scatter and bincount: index_mode.hip.h):
 //   * the merging of a view's axes and the canonical walk out[o, i] = f_r a[o*so + r*sr + i*si] it may come to (Canon, ROW / COLUMN);
 //   * lanes per short row (segment_lanes; segment_for where whole rows are copied) and the cutting of R into chunks when a launch
