@@ -121,6 +121,7 @@ struct FusionStats {
     unsigned long long selects = 0;             // smhip_where / smhip_select_count / smhip_select calls
     unsigned long long uniques = 0;             // smhip_runs_count / smhip_runs calls: unique_* / unique_consecutive / run_lengths (a count, then the runs)
     unsigned long long topks = 0;               // smhip_topk_axis calls: topk / topk_flat
+    unsigned long long softmaxes = 0;           // smhip_softmax_axis calls: softmax / log_softmax / logsumexp
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -831,6 +832,20 @@ public:
     std::pair<SMArray, SMArray<std::int64_t>> max_with_index(int axis, bool keepdims = false) const { return arg_of(SMHIP_ARG_MAX, axis, keepdims, true); }
     std::pair<SMArray, SMArray<std::int64_t>> min_with_index(int axis, bool keepdims = false) const { return arg_of(SMHIP_ARG_MIN, axis, keepdims, true); }
 
+    // The NORMALISATION those pipelines start from, fused per line: softmax(x)_r = exp(x_r - m) / S, log_softmax(x)_r = (x_r - m) - ln S and
+    // logsumexp(x) = m + ln S along `axis`, with m the line's maximum and S the fp64 sum of the exp(x_r - m); float and double only (a
+    // static_assert).  softmax and log_softmax have this array's shape; logsumexp has the kept shape (keepdims keeps the axis as an
+    // extent of 1), and without an axis runs over the row-major flattening, shape {1}.  A NaN in a line, or a maximum that is not
+    // finite, gives NaN (logsumexp: the maximum itself); the differences are formed in fp64, every result is rounded once
+    // (smhip.h, "softmax", has the bounds).  `axis` counts from the end when negative and is the last one by default; an axis out of
+    // range throws std::runtime_error.  The operand may be a view (a transposed one is read in place) or a pending operator chain
+    // (evaluated first); each is ONE smhip_softmax_axis call (counted in sm::fusion_stats().softmaxes) whose result stays on the
+    // device and feeds the next chain, argmax or take_along_axis.
+    SMArray softmax(int axis = -1) const { return softmax_of(SMHIP_SOFTMAX, axis, false); }
+    SMArray log_softmax(int axis = -1) const { return softmax_of(SMHIP_LOG_SOFTMAX, axis, false); }
+    SMArray logsumexp(int axis, bool keepdims = false) const { return softmax_of(SMHIP_LOGSUMEXP, axis, keepdims); }
+    SMArray logsumexp() const { return softmax_of(SMHIP_LOGSUMEXP, std::nullopt, false); }
+
     // The ORDER along an axis (np.sort / np.argsort with kind="stable"): sort gives the elements of each line in order, argsort
     // their positions along `axis` as std::int64_t; both have this array's shape and are resident on the device.  Ascending puts
     // the smaller values first and NaNs last (-0 == +0, all NaNs tie); descending = true puts NaNs, then the larger values first.
@@ -1439,6 +1454,18 @@ private:
                                    in.ndim(), in.axis, want_values ? r.first.device_data_mut() : nullptr, want_where ? r.second.device_data_mut() : nullptr));
         ++detail::tls_fusion_stats.sorts;
         return r;
+    }
+
+    // softmax / log_softmax: of this array's shape; logsumexp: of the kept shape (without an axis: the flattening's, shape {1}).
+    SMArray softmax_of(int kind, std::optional<int> axis, bool keepdims) const {
+        static_assert(std::is_floating_point_v<T>, "softmax / log_softmax / logsumexp: float and double only");
+        axis = line_axis(axis);
+        hip::DeviceGuard on(device());
+        const AbiView in = line(axis);  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(kind != SMHIP_LOGSUMEXP ? std::vector<std::size_t>(_shape) : axis ? kept_shape(1u << *axis, keepdims) : std::vector<std::size_t>{1});
+        hip::check(smhip_softmax_axis(kind, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), in.axis, out.device_data_mut()));
+        ++detail::tls_fusion_stats.softmaxes;
+        return out;
     }
 
     // {the first k of the order, their positions}, of this array's shape with k on the axis (without an axis: of {k}).

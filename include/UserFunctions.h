@@ -283,6 +283,18 @@ std::pair<SMArray<T>, SMArray<std::int64_t>> topk(const SMArray<T> &arr, std::si
 template <typename T>
 std::pair<SMArray<T>, SMArray<std::int64_t>> topk_flat(const SMArray<T> &arr, std::size_t k, bool largest = true) { return arr.topk_flat(k, largest); }
 
+// softmax, log_softmax and logsumexp along an axis, fused per line (float and double): one library call each instead of the
+// max / exp / sum / divide recipe.  logsumexp without an axis runs over the row-major flattening, shape {1}.  Semantics as
+// SMArray::softmax (SMArray.h) and smhip_softmax_axis.
+template <typename T>
+SMArray<T> softmax(const SMArray<T> &arr, int axis = -1) { return arr.softmax(axis); }
+template <typename T>
+SMArray<T> log_softmax(const SMArray<T> &arr, int axis = -1) { return arr.log_softmax(axis); }
+template <typename T>
+SMArray<T> logsumexp(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.logsumexp(axis, keepdims); }
+template <typename T>
+SMArray<T> logsumexp(const SMArray<T> &arr) { return arr.logsumexp(); }
+
 // Picking by position along an axis (np.take_along_axis / np.take): result[..., j, ...] = arr[..., idx[..., j, ...], ...].
 // take_along_axis: `idx` has arr's rank, its other axes equal to arr's or broadcastable; without an axis both are flattened.
 // take: `idx` is 1-D, the result is arr's shape with `axis` replaced by idx.size(); take_flat indexes the row-major flattening.

@@ -552,6 +552,55 @@ int smhip_topk_axis(int order, int dtype, const void *a, const int64_t *shape, c
 int smhip_topk_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int64_t k,
                     int *route, int *launches, int64_t *ori3, int64_t *info3);
 
+/* --------------------------------------- softmax / log_softmax / logsumexp */
+/* Along ONE axis, fused per line, f32 and f64.  For a line x_0 .. x_{R-1} with maximum m and d_r = x_r - m:
+ *   the line              SOFTMAX            LOG_SOFTMAX        LOGSUMEXP
+ *   holds a NaN           NaN everywhere     NaN everywhere     NaN
+ *   m = +inf              NaN everywhere     NaN everywhere     +inf
+ *   m = -inf (all -inf)   NaN everywhere     NaN everywhere     -inf
+ *   otherwise             e_r / S            d_r - ln S         m + ln S        with e_r = exp(d_r), S = the sum of the e_r
+ *   R = 0                 nothing written    nothing written    every output -inf
+ * In the ordinary case d_r is formed in fp64; f32: it enters the exp core on its fp64 side without passing through f32, d_r < -104
+ * gives e_r = +0, e_r is the core's f32 result; f64: e_r is the library's f64 exp.  S is the fp64 sum of the e_r in a fixed order;
+ * ln S is ONE f64 logarithm per line (the library's own); the quotient, d_r - ln S and m + ln S are each formed in fp64 and rounded
+ * once.  So e = 1 exactly at the maximum, a constant line of R gives float(1.0 / (double)R) (f64: 1.0 / R) exactly, and R == 1 gives
+ * 1, +0 and x_0.  Where a line is cut into chunks, a chunk's sum is rescaled by exp(m_c - m) computed in fp64 by the f64 exp, one
+ * factor per chunk.  The bits depend on kind, dtype, shape and layout after merging axes only: not on the run, the stream or the
+ * grid (no float atomics).
+ * Error bounds (derived from exp and log each being <= 1 ULP, not measured), u = 2^-24 (f32) or 2^-53 (f64), tiny = the smallest
+ * subnormal, D = min(746, max_k |d_k|), exact = the true value for the given inputs:
+ *                  f32                        f64
+ *   SOFTMAX        6u exact + 2 tiny          u (R + 5 + |d_r| + D) exact + 2 tiny
+ *   LOG_SOFTMAX    2.5u + u |exact|           u (R + 1 + D + |d_r| + |exact|) + 2u max(1, ln R)
+ *   LOGSUMEXP      2.5u + u |exact|           u (R + 1 + D + |exact|) + 2u max(1, ln R)
+ * (f32 softmax: one ULP each for numerator and denominator and half of one for the final rounding are 5u; every term of S is
+ * positive, so S inherits at most one ULP and ln S is off by at most 2u absolute; f64 adds the rounding of d and the (R - 1) u any
+ * summation order can cost.) */
+typedef enum smhip_softmax_kind { SMHIP_SOFTMAX = 0, SMHIP_LOG_SOFTMAX = 1, SMHIP_LOGSUMEXP = 2 } smhip_softmax_kind;
+/* `a` is any view (strides in ELEMENTS, >= 0, 0 broadcasts; rank 1 .. SMHIP_MAX_NDIM); `axis` in [0, ndim), not counted from the
+ * end.  `out` is dense row-major: over `shape` for SOFTMAX and LOG_SOFTMAX; for LOGSUMEXP over the other axes in their order, as
+ * smhip_reduce_axes writes it (1 element when ndim == 1).  out == a is allowed for SOFTMAX / LOG_SOFTMAX when `a` is dense (in
+ * place); any other overlap is SMHIP_ERR_INVALID.  i32 / i64: SMHIP_ERR_UNSUPPORTED.  Checked before any device is touched
+ * (SMHIP_ERR_INVALID): kind, dtype, ndim, axis, negative extents or strides, null shape / strides, a null buffer with something to
+ * write.  Asynchronous, stream-ordered; recorded tiny operators are flushed first, so a small call runs at once behind them. */
+int smhip_softmax_axis(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *out);
+/* Host only, no device touched: the route smhip_softmax_axis would take.  *route = a kernel id (SMHIP_SOFTMAX_ROUTE_*) ORed with the
+ * flags below; *launches = the kernel launches of the whole call; ori3 = {O, R, I} after merging (R is exactly shape[axis]);
+ * info3 = {L, reads, levels}: L the longest line held on chip for this dtype (8192 f32, 4096 f64), reads how often the ROUTE reads
+ * the operand from memory (1 exactly when the line is held; 2 ROW SPLIT -- LOGSUMEXP stops after the first of them; 3 COLUMN), levels
+ * the launches of the first pass (1; 2 with SPLIT: the chunks, then their combination).  Any output may be NULL. */
+#define SMHIP_SOFTMAX_ROUTE_NONE 0    /* nothing to write */
+#define SMHIP_SOFTMAX_ROUTE_ROW 1     /* I = 1, sr = 1, the result's lines contiguous: R <= L held in registers, ONE launch -- a segment of
+                                         4 / 16 / 64 lanes, a wave or a workgroup per line */
+#define SMHIP_SOFTMAX_ROUTE_COLUMN 2  /* I > 1, si = 1: a lane owns the 16 bytes of consecutive columns and walks R three times */
+#define SMHIP_SOFTMAX_ROUTE_FILL 3    /* LOGSUMEXP over an empty axis: -inf */
+#define SMHIP_SOFTMAX_SPLIT 0x100     /* ROW: R > L, the line streamed; COLUMN: too few lanes.  R is cut into chunks whose (m, S) pairs go to
+                                         a pooled fp64 buffer and are combined in chunk order; a last launch reads x again and writes */
+#define SMHIP_SOFTMAX_COPY 0x200      /* the operand is copied dense first (no unit stride in the walk, a stepped or stride-0 axis, a ROW
+                                         walk whose result lines would be strided) */
+int smhip_softmax_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                       int *route, int *launches, int64_t *ori3, int64_t *info3);
+
 /* ------------------------------------------------ take / take_along_axis */
 /* Picking by position along ONE axis, np.take_along_axis:  out[..., j, ...] = a[..., idx[..., j, ...], ...].  np.take(a, ids,
  * axis) is the same call with the 1-D index array broadcast (stride 0) over every axis but `axis`.  The contract:

@@ -56,6 +56,11 @@ SORT_MERGE, SORT_COPY = 0x100, 0x200
 TOPK_ROUTE_NONE, TOPK_ROUTE_COPYONLY, TOPK_ROUTE_ROW, TOPK_ROUTE_SORT = range(4)
 TOPK_TILED, TOPK_COPY = 0x100, 0x200
 TOPK_RANKED = 128  # SMHIP_TOPK_RANKED: the longest line that is ranked, whatever k is
+# smhip_softmax_kind, and smhip_softmax_plan's route word: a kernel id in the low byte, flags above it
+SOFTMAX, LOG_SOFTMAX, LOGSUMEXP = range(3)
+SOFTMAX_KINDS = {"softmax": SOFTMAX, "log_softmax": LOG_SOFTMAX, "logsumexp": LOGSUMEXP}
+SOFTMAX_ROUTE_NONE, SOFTMAX_ROUTE_ROW, SOFTMAX_ROUTE_COLUMN, SOFTMAX_ROUTE_FILL = range(4)
+SOFTMAX_SPLIT, SOFTMAX_COPY = 0x100, 0x200
 INDEX_CHECKED, INDEX_CLIP, INDEX_WRAP = range(3)  # smhip_index_mode
 INDEX_MODES = {"checked": INDEX_CHECKED, "raise": INDEX_CHECKED, "clip": INDEX_CLIP, "wrap": INDEX_WRAP}
 # smhip_take_plan's route word: a kernel id in the low byte, the flag above it
@@ -886,6 +891,69 @@ class Smhip:
         route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
         self._ck(self.c.smhip_topk_plan(C.c_int(SORT_DESCENDING if largest else SORT_ASCENDING), C.c_int(dtype), _i64(shape), _i64(strides),
                                         C.c_int(len(shape)), C.c_int(int(axis)), C.c_int64(int(k)), C.byref(route), C.byref(launches), ori, info))
+        return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
+
+    def softmax(self, a: DeviceArray, axis=-1, out: DeviceArray | None = None):
+        """softmax of `a` (any view, float32 or float64) along `axis`, one fused call -> a new dense DeviceArray of a's shape, or into
+        `out`, a dense array of a's shape and dtype; `out` may be `a` itself when `a` is dense (in place).  axis=None takes the row-major
+        flattening and gives shape (a.size,).  TypeError for an integer dtype, ValueError for a bad axis or out."""
+        return self._softmax(SOFTMAX, "softmax", a, axis, False, out)
+
+    def log_softmax(self, a: DeviceArray, axis=-1, out: DeviceArray | None = None):
+        """log(softmax(a, axis)) without forming the softmax: (x - max) - log(sum(exp(x - max))), rounded once; arguments as softmax()."""
+        return self._softmax(LOG_SOFTMAX, "log_softmax", a, axis, False, out)
+
+    def logsumexp(self, a: DeviceArray, axis=-1, keepdims=False, out: DeviceArray | None = None):
+        """log(sum(exp(a), axis)) -> a new dense DeviceArray over the other axes (keepdims=True: with extent 1 along the axis), or into
+        `out`, a dense array of that shape and a's dtype, never the operand.  axis=None runs over the row-major flattening: shape (1,)."""
+        return self._softmax(LOGSUMEXP, "logsumexp", a, axis, keepdims, out)
+
+    def _softmax(self, kind, name, a, axis, keepdims, out):
+        if a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError(f"{name}: dtype {a.dtype} (float32 and float64 only)")
+        if axis is None:
+            if not a.is_dense():  # the row-major order of a view: its dense copy
+                if out is a:
+                    raise ValueError(f"{name}: out=a (in place) needs a dense array")
+                dense = self.empty(a.shape, a.dtype)
+                self.assign(dense, a)
+                a = dense
+            shape, strides, axis = (a.size,), (1,), 0
+        else:
+            (axis,) = self._axes(a.ndim, int(axis))
+            shape, strides = tuple(a.shape), tuple(a.strides)
+        if kind == LOGSUMEXP:
+            result_shape = shape[:axis] + ((1,) if keepdims else ()) + shape[axis + 1:]
+            if not result_shape:
+                result_shape = (1,)
+        else:
+            result_shape = shape
+        if out is None:
+            out = self.empty(result_shape, a.dtype)
+        elif out is a and kind != LOGSUMEXP:
+            if not a.is_dense():
+                raise ValueError(f"{name}: out=a (in place) needs a dense array")
+        elif out.dtype != a.dtype or tuple(out.shape) != tuple(result_shape) or not out.is_dense():
+            raise ValueError(f"{name}: out must be a dense {a.dtype} array of shape {tuple(result_shape)}; "
+                             f"got {out.dtype} {tuple(out.shape)} dense={out.is_dense()}")
+        self._ck(self.c.smhip_softmax_axis(C.c_int(kind), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(shape), _i64(strides), C.c_int(len(shape)),
+                                           C.c_int(axis), C.c_void_p(out.ptr)))
+        return out
+
+    def softmax_raw(self, kind, dtype, a_ptr, shape, strides, axis, out_ptr=0, ndim=None):
+        """smhip_softmax_axis with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        return self.c.smhip_softmax_axis(C.c_int(kind), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                         _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_int(axis), C.c_void_p(out_ptr))
+
+    def softmax_plan(self, kind, dtype, shape, strides, axis):
+        """smhip_softmax_plan (host only): (route word, launches, (O, R, I), (L, reads, levels)) for a call on shape / strides (elements)."""
+        kind = SOFTMAX_KINDS[kind] if isinstance(kind, str) else int(kind)
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        self._ck(self.c.smhip_softmax_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)),
+                                           C.byref(route), C.byref(launches), ori, info))
         return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
 
     def take_along_axis(self, a: DeviceArray, idx: DeviceArray, axis, mode="checked", out: DeviceArray | None = None):

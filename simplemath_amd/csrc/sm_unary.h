@@ -49,13 +49,15 @@ SM_UNARY_CONST kScale[2] = {0x1.71547652b82fep+0, 0x1.62e42fefa39efp-1};
 
 // ------------------------------------------------------------------------------------------------------------ f32 exp
 // 2^(x log2 e) for W finite x with |x| <= 104 (n within [-151, 151]: ldexp covers overflow and the subnormal range).
+// The entry with the argument in fp64 (sm_softmax.h: a difference x - m that f32 cannot hold goes in without being rounded to it);
+// the f32 entry below widens and comes here, so both are the same arithmetic.
 template <int W>
-SM_POW_FN void expf_core_n(const float (&x)[W], float (&out)[W]) {
+SM_POW_FN void expf_core_n(const double (&x)[W], float (&out)[W]) {
     float ff[W];
     int ni[W];
 #pragma unroll
     for (int k = 0; k < W; ++k) {
-        const double E = (double)x[k] * kScale[0];
+        const double E = x[k] * kScale[0];
         const double n = SM_POW_RINT(E);
         ff[k] = (float)(E - n);  // |f| <= 1/2
         ni[k] = smpow::sat_i32(n);
@@ -93,6 +95,13 @@ SM_POW_FN void expf_core_n(const float (&x)[W], float (&out)[W]) {
     }
 #pragma unroll
     for (int k = 0; k < W; ++k) out[k] = SM_POW_LDEXPF(qf[k], ni[k]);
+}
+template <int W>
+SM_POW_FN void expf_core_n(const float (&x)[W], float (&out)[W]) {
+    double xd[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) xd[k] = (double)x[k];
+    expf_core_n<W>(xd, out);
 }
 
 // e^x for W independent x.  Ordinary <=> |x| <= 104 (finite): exp(-104) = 2^-150.04 already rounds to +0 and exp(89) is
