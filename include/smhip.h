@@ -174,7 +174,8 @@ int smhip_fused_expr_sum_async(const char *hip_expression, int dtype, const void
                                const void *scalars_host, int n_scalars, void *out_or_null, size_t n, double *sum_dev);
 /* SMArray's element-copy assignment `dst_view = src` (SMArray.h:89-97, a host loop in the reference):
  * dst[sum idx_k*dst_strides_k] = src[sum idx_k*src_strides_k] over `shape`.  A source stride may be 0 (broadcast);
- * a destination stride may not (for extents > 1).  Source and destination must not overlap. */
+ * a destination stride may not (for extents > 1).  An empty shape is a no-op, whatever the strides and pointers.  Source and
+ * destination must not overlap. */
 int smhip_copy_strided(int dtype, const void *src, const int64_t *src_strides, void *dst, const int64_t *dst_strides,
                        const int64_t *shape, int ndim);
 /* handle_contiguous_arrays<T,Op> (calculate.h:101-134): out[i] = a[i] op b[i]. */

@@ -1130,10 +1130,12 @@ class Smhip:
         nd = len(out_shape)
         walk = [J if d == axis else out_shape[d] for d in range(nd)]
         if isinstance(values, DeviceArray):
-            res = self.broadcast(walk, [0] * nd, values.shape, values.strides)
-            if res is None or list(res[0]) != list(walk):
+            # numpy's rule, right-aligned: an extent of the values is the walk's or 1 (sm::broadcast, which smhip_broadcast follows, has no
+            # empty extents: against (7, 0) it turns (7, 1) into (7, 1), and a call without entries would be refused here)
+            pad = nd - values.ndim
+            if pad < 0 or any(n != want and n != 1 for n, want in zip(values.shape, walk[pad:])):
                 raise ValueError(f"{who}: values of shape {values.shape} do not broadcast to {tuple(walk)}")
-            sv = [s if n != 1 else 0 for s, n in zip(res[2], walk)]
+            sv = [0] * pad + [st if n == want and n != 1 else 0 for n, st, want in zip(values.shape, values.strides, walk[pad:])]
         else:
             values = self.to_device(np.array([values], dtype=a.dtype))
             sv = [0] * nd

@@ -1137,10 +1137,11 @@ int smhip_copy_strided(int dtype, const void *src, const int64_t *src_strides, v
     int64_t n = 1;
     for (int i = 0; i < ndim; ++i) {
         if (shape[i] < 0 || src_strides[i] < 0 || dst_strides[i] < 0) return fail(SMHIP_ERR_INVALID, "copy_strided: negative extent or stride at dim %d", i);
-        if (shape[i] > 1 && dst_strides[i] == 0) return fail(SMHIP_ERR_INVALID, "copy_strided: destination stride 0 at dim %d (elements would overwrite each other)", i);
         n *= shape[i];
     }
-    if (n == 0) return SMHIP_OK;
+    if (n == 0) return SMHIP_OK;  // nothing to copy, whatever the strides: the dense strides of an empty shape hold zeros
+    for (int i = 0; i < ndim; ++i)
+        if (shape[i] > 1 && dst_strides[i] == 0) return fail(SMHIP_ERR_INVALID, "copy_strided: destination stride 0 at dim %d (elements would overwrite each other)", i);
     if (!src || !dst) return fail(SMHIP_ERR_INVALID, "copy_strided: null buffer");
     const size_t esz = dtype_size(dtype);
     if ((int64_t)n <= kTinyMaxResults) {

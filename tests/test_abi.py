@@ -78,6 +78,19 @@ def test_argument_validation_needs_no_gpu(lib):
     assert e.value.code == sma.ERR_INVALID and "MAX_NDIM" in str(e.value)
 
 
+def test_copy_strided_of_an_empty_shape_is_a_no_op(lib):
+    """The dense row-major strides of an empty shape hold zeros ((5, 0): (0, 1)), and nothing can overwrite anything: the copy
+    returns before it looks at the destination's strides or at a device.  Found by tests/fuzz_axis.py, whose empty views that are
+    not dense go through this copy (unique, and every axis=None form)."""
+    import ctypes as C
+    arr = lambda *v: (C.c_int64 * len(v))(*v)  # noqa: E731
+    for shape, src, dst in (((5, 0), (7, 1), (0, 1)), ((2, 0, 3), (40, 6, 1), (0, 3, 1)), ((0,), (3,), (0,))):
+        assert lib.c.smhip_copy_strided(sma.F32, C.c_void_p(16), arr(*src), C.c_void_p(32), arr(*dst), arr(*shape), len(shape)) == 0, shape
+    # with something to copy a destination stride of 0 is still refused
+    assert lib.c.smhip_copy_strided(sma.F32, C.c_void_p(16), arr(7, 1), C.c_void_p(32), arr(0, 1), arr(5, 2), 2) == sma.ERR_INVALID
+    assert "destination stride 0 at dim 0" in lib.c.smhip_last_error().decode()
+
+
 def test_no_cpu_fallback(lib):
     """Without a HIP device the product fails loudly (never routes to the oracle)."""
     if _has_gpu(lib):

@@ -19,8 +19,8 @@ steps 1-4 took.  K_BALLAST = 10 chains of STAGES = 14 stages on 96 MiB: see MEAS
 Scenarios run in a fresh child process per test (an earlier test of the pytest process may have switched the device to one
 queue for good); the child refuses to start unless queue_stats() reports two queues.
 
-fill and the uniform fill read nothing: they play P in RAW and C in WAR / WAW only (behind gate_read a writer is held back by a
-WAR dependency alone, which is what the WAW scenarios test).
+fill, the uniform fill and the Generator's draw (smhip_random, "random") read nothing: they play P in RAW and C in WAR / WAW only
+(behind gate_read a writer is held back by a WAR dependency alone, which is what the WAW scenarios test).
 """
 import json
 import os
@@ -48,7 +48,8 @@ issuing steps 1-4 took 0.46-0.74 ms per scenario (1.3 ms for a process's very fi
 a chain on more than 112 MiB would leave the two-queue range -- so K only sets the length of the window.
 
 Sensitivity: the file run once against libraries built with one piece of queue_order.h's ordering removed (no kernel and no
-address differs, so they can only give wrong values).  Red = the scenario failed its bit-for-bit comparison.
+address differs, so they can only give wrong values).  Red = the scenario failed its bit-for-bit comparison.  The counts below
+were measured before the "random" entry joined ENTRIES (18 entries then, 19 now) and have not been measured again.
   RAW loop of dependencies() removed    every "raw:" scenario between two tracked entry points (13 of 18; the 5 with a barrier
                                         operator on one side are ordered by the barrier), every "span: RAW" scenario but the
                                         operator under 1 MiB (a barrier), the operator over 224 MiB; nothing else.
@@ -87,6 +88,7 @@ def _child(group):
     import simplemath_amd as sma
     from oracle import oracle as orc
     from simplemath_amd import DeviceArray
+    from tests import random_model
 
     lib = sma.load()
     lib.set_device(0)
@@ -209,6 +211,9 @@ def _child(group):
         "copy": (True, lambda s, d, a: lib.copy(d.ptr, s.ptr, N * 4), lambda s, a, d0: s),
         "fill": (False, lambda s, d, a: fill(d, 3.25), lambda s, a, d0: np.full(N, 3.25, f32)),
         "fill_uniform": (False, lambda s, d, a: lib._ck(lib.c.smhip_fill_uniform_f32(C.c_void_p(d.ptr), N, 11, 0, -1.0, 1.0)), lambda s, a, d0: uniform_ref()),
+        # the Generator's draw (smhip_random: a write span and nothing read), its bytes from the CPU model of tests/random_model.py
+        "random": (False, lambda s, d, a: lib._ck(lib.random_raw(sma.RANDOM_UNIFORM, sma.F32, d.ptr, N, 29, 3, 5, (-2.0, 6.0))),
+                   lambda s, a, d0: random_model.draw("uniform", f32, 29, 3, 5, N, (-2.0, 6.0))),
         "elementwise": (True, lambda s, d, a: lib.binary(sma.OP_ADD, v2(s), v2(a, (1, COLS)), out=v2(d)),
                         lambda s, a, d0: (s.reshape(ROWS, COLS) + a[:COLS].reshape(1, COLS)).reshape(-1)),
         "copy_strided": (True, lambda s, d, a: lib.assign(v2(d), v2(s, (ROWS, COLS), (1, ROWS))), lambda s, a, d0: s.reshape(COLS, ROWS).T.reshape(-1)),

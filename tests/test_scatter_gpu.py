@@ -490,3 +490,21 @@ def test_empty_cases(smhip):
         lib.put_along_axis(hollow, lib.to_device(np.zeros((4, 2), np.int64)), vals, 1)
     with pytest.raises(IndexError):
         lib.index_add(hollow, lib.to_device(np.zeros(2, np.int64)), 1.0, 1)
+
+
+def test_no_entries_with_values_that_broadcast_along_the_axis(smhip):
+    """J = 0 with a values array of extent 1 along the axis: numpy broadcasts (7, 1) against (7, 0) to (7, 0) and writes nothing.  The
+    binding used to refuse it (it asked sm::broadcast, which has no empty extents).  Found by tests/fuzz_axis.py, seed 7."""
+    lib = smhip
+    a = distinct((7, 9), np.float32)
+    none = lib.to_device(np.zeros(1, np.int64))
+    none = sma.DeviceArray(lib, none.base_ptr, np.int64, (7, 0), (0, 1), 0, none._owner)
+    for shape in ((7, 1), (1, 1), (1,), (7, 0)):
+        vals = lib.to_device(np.ones(max(1, int(np.prod(shape))), np.float32))
+        vals = sma.DeviceArray(lib, vals.base_ptr, np.float32, shape, (1,) * len(shape), 0, vals._owner)
+        for fn in (lib.put_along_axis, lib.scatter_add):
+            d = lib.to_device(a)
+            assert fn(d, none, vals, 1, mode="clip") is d and d.numpy().tobytes() == a.tobytes(), shape
+    with pytest.raises(ValueError):   # still refused: neither the walk's extent nor 1
+        lib.put_along_axis(lib.to_device(a), none, lib.to_device(np.ones((7, 2), np.float32)), 1)
+

@@ -359,6 +359,21 @@ def test_empty_operands(smhip):
         assert values.shape == counts.shape == (0,)
 
 
+def test_empty_views_that_are_not_dense(smhip):
+    """base[:, 3:3] keeps base's row stride, so it is copied dense before it is flattened: that copy of nothing used to be refused
+    ("destination stride 0": the dense strides of (5, 0) are (0, 1)).  Found by tests/fuzz_axis.py, seed 7."""
+    lib = smhip
+    base = np.arange(35, dtype=np.float32).reshape(5, 7)
+    d = lib.to_device(base)
+    for view in (base[:, 3:3], base[1:4:2, 5:5], base.T[:, 2:2], base.reshape(5, 7, 1)[:, 2:2, :]):
+        dv = d.view_like(view, base)
+        assert not dv.is_dense() and dv.size == 0
+        values, index, inverse, counts = lib.unique(dv, return_index=True, return_inverse=True, return_counts=True)
+        assert values.shape == index.shape == counts.shape == (0,) and inverse.shape == view.shape
+        assert lib.unique_consecutive(dv).shape == (0,)
+        assert lib.sort(dv, axis=None).shape == (0,) and lib.scan("cumsum", dv, axis=None).shape == (0,)
+
+
 def test_group_by_through_index_add(smhip):
     """The keys' inverse fed to index_add: a sum per key, against np.add.at."""
     lib = smhip
