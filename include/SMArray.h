@@ -643,23 +643,28 @@ private:
     template <typename Op>
     void apply_scalar_into(T value, SMArray &out) const {
         {
-            if (!_shape.empty() && totalSize <= SMHIP_INLINE_MAX_OUTPUTS && host_only_small() && hip::device_op<Op>::id() <= SMHIP_OP_POW) {
+            // The destination first: taking it runs the chain pending on this thread, and that chain may have THIS array among its
+            // operands and upload it.  Whether the array is host-only (and rides inline) is decided after that, once, and the pointer
+            // and the byte count passed below come from that one answer -- in an argument list their order of evaluation is not fixed,
+            // and a host pointer passed with a count of 0 is read as a device pointer.
+            T *dst = out.device_data_mut();
+            const std::size_t host_bytes = !_shape.empty() && totalSize <= SMHIP_INLINE_MAX_OUTPUTS && hip::device_op<Op>::id() <= SMHIP_OP_POW ? host_only_small() : 0;
+            if (host_bytes) {
                 // host-built tiny array op scalar: both ride in the launch packet
                 const auto sa = hip::to_i64(_strides), sh = hip::to_i64(_shape);
                 const std::vector<std::int64_t> zeros(sh.size(), 0);
-                hip::check(smhip_elementwise_inline(hip::device_op<Op>::id(), hip::dtype_of<T>::id, data.read(), host_only_small(), sa.data(),
-                                                    &value, sizeof(T), zeros.data(), sh.data(), static_cast<int>(sh.size()),
-                                                    out.device_data_mut()));
+                hip::check(smhip_elementwise_inline(hip::device_op<Op>::id(), hip::dtype_of<T>::id, data.read(), host_bytes, sa.data(),
+                                                    &value, sizeof(T), zeros.data(), sh.data(), static_cast<int>(sh.size()), dst));
                 ++data.storage()->inline_uses;
                 return;
             }
             if (is_dense()) {
-                hip::array_scalar_op_device<T, Op>(device_data(), value, totalSize, out.device_data_mut());
+                hip::array_scalar_op_device<T, Op>(device_data(), value, totalSize, dst);
             } else {  // a view: honour its strides (the reference reads views as flat here)
                 hip::DeviceBuffer s(sizeof(T));
                 hip::check(smhip_upload(s.get(), &value, sizeof(T)));
                 hip::element_wise_op_device<T, Op>(device_data(), _strides, s.template as<T>(),
-                                                   std::vector<std::size_t>(_shape.size(), 0), out.device_data_mut(), _shape);
+                                                   std::vector<std::size_t>(_shape.size(), 0), dst, _shape);
             }
         }
     }

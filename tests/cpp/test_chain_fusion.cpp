@@ -301,6 +301,18 @@ static void ordering() {
     CHECK(pw(0, 0) == 4.0f);
     CHECK(((p + p) * 2.0f) % p == 64.0f);
     CHECK(((p + p) * 2.0f).sum() == 64.0);
+    {   // fuzz_surface --seed 20262 --case 18 (a GPU memory fault): sm::pow of a host-built tiny array that is also an operand of the
+        // chain pending in the same expression.  Taking pow's destination runs that chain, which uploads the array; the inline path then
+        // passed the array's HOST pointer with a byte count of 0, "a device pointer".  (x).operator*(y) fixes the order the fuzz case
+        // had: the object expression is sequenced before the argument, so the chain is pending when pow runs.
+        sm::SMArray<std::int32_t> ha(new std::int32_t[24], {2, 12});
+        for (int i = 0; i < 24; ++i) ha.data[i] = i - 7;                     // host only, 96 bytes
+        auto hb = sm::ones<std::int32_t>(2, 12);
+        auto hr = (hb * 6 - ha).operator*(sm::pow(ha, 2));                   // (6 - a) * a^2
+        bool same = true;
+        for (int i = 0; i < 24; ++i) same = same && hr.cdata()[i] == (6 - (i - 7)) * (i - 7) * (i - 7);
+        CHECK(same);
+    }
     // a function taking const SMArray& gets a computed value
     auto f = [](const sm::SMArray<float> &v) { return v(0, 0) + v(3, 3); };
     CHECK(f((p + p) * 3.0f) == 12.0f);
