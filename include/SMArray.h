@@ -122,6 +122,7 @@ struct FusionStats {
     unsigned long long uniques = 0;             // smhip_runs_count / smhip_runs calls: unique_* / unique_consecutive / run_lengths (a count, then the runs)
     unsigned long long topks = 0;               // smhip_topk_axis calls: topk / topk_flat
     unsigned long long softmaxes = 0;           // smhip_softmax_axis calls: softmax / log_softmax / logsumexp
+    unsigned long long moments = 0;             // smhip_moments_axes / smhip_standardize_axis calls: var / stddev / var_mean / standardize
 };
 inline thread_local FusionStats tls_fusion_stats;
 // The end of a full-expression, seen from the destructor of one of its temporaries.
@@ -851,6 +852,40 @@ public:
     SMArray logsumexp(int axis, bool keepdims = false) const { return softmax_of(SMHIP_LOGSUMEXP, axis, keepdims); }
     SMArray logsumexp() const { return softmax_of(SMHIP_LOGSUMEXP, std::nullopt, false); }
 
+    // The SECOND MOMENT along axes (np.var / np.std with `axis` and `ddof`), centred in fp64: the fp64 mean, d = x - mean in fp64,
+    // M2 = sum d^2 - (sum d)^2 / N, var = M2 / (N - ddof) and stddev its fp64 square root, each rounded once; float and double only (a
+    // static_assert; astype first).  Data on a large offset keep every digit (smhip.h, "var / std / standardize", has the bounds), a
+    // constant line gives exactly +0, a NaN or an infinity in a line NaN.  var_mean returns {var, mean} from one call, the mean bit for
+    // bit mean(axes)'s.  standardize(axis, eps, ddof) is (x - mean) / sqrt(var + eps) along ONE axis (the last by default), of this
+    // array's shape, the statistics and the quotient in fp64: layer normalisation without its affine part, in one read for a line the
+    // library holds in registers.  Axes count from the end when negative; keepdims keeps each reduced axis as an extent of 1; the forms
+    // without an axis run over the row-major flattening and give shape {1}.  A bad or repeated axis, ddof < 0, N - ddof <= 0 (with
+    // something to write) and a negative, NaN or infinite eps throw std::runtime_error.  A pending operator chain as the operand is
+    // evaluated first; each is ONE library call (counted in sm::fusion_stats().moments) whose result stays on the device.
+    SMArray var(int axis, std::int64_t ddof = 0, bool keepdims = false) const { return var(std::initializer_list<int>{axis}, ddof, keepdims); }
+    SMArray var(std::initializer_list<int> axes, std::int64_t ddof = 0, bool keepdims = false) const { return moments_of(SMHIP_MOMENT_VAR, &axes, ddof, keepdims, false).first; }
+    SMArray var() const { return moments_of(SMHIP_MOMENT_VAR, nullptr, 0, false, false).first; }
+    SMArray stddev(int axis, std::int64_t ddof = 0, bool keepdims = false) const { return stddev(std::initializer_list<int>{axis}, ddof, keepdims); }
+    SMArray stddev(std::initializer_list<int> axes, std::int64_t ddof = 0, bool keepdims = false) const { return moments_of(SMHIP_MOMENT_STD, &axes, ddof, keepdims, false).first; }
+    SMArray stddev() const { return moments_of(SMHIP_MOMENT_STD, nullptr, 0, false, false).first; }
+    std::pair<SMArray, SMArray> var_mean(int axis, std::int64_t ddof = 0, bool keepdims = false) const { return var_mean(std::initializer_list<int>{axis}, ddof, keepdims); }
+    std::pair<SMArray, SMArray> var_mean(std::initializer_list<int> axes, std::int64_t ddof = 0, bool keepdims = false) const { return moments_of(SMHIP_MOMENT_VAR, &axes, ddof, keepdims, true); }
+    std::pair<SMArray, SMArray> var_mean() const { return moments_of(SMHIP_MOMENT_VAR, nullptr, 0, false, true); }
+    SMArray standardize(int axis = -1, double eps = 0.0, std::int64_t ddof = 0) const {
+        static_assert(std::is_floating_point_v<T>, "standardize: float and double only (astype first)");
+        const int a = detail::normal_axis<std::runtime_error>(axis, _shape.size());
+        if (!(eps >= 0.0) || eps > std::numeric_limits<double>::max()) throw std::runtime_error("simpleMath/MI355X: standardize: eps is negative, NaN or infinite");
+        if (ddof < 0) throw std::runtime_error("simpleMath/MI355X: standardize: ddof " + std::to_string(ddof) + " is negative");
+        if (totalSize && static_cast<std::int64_t>(_shape[a]) - ddof <= 0)
+            throw std::runtime_error("simpleMath/MI355X: standardize: N - ddof = " + std::to_string(_shape[a]) + " - " + std::to_string(ddof) + " is not positive");
+        hip::DeviceGuard on(device());
+        const AbiView in = along_axis(a);  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(std::vector<std::size_t>(_shape));
+        hip::check(smhip_standardize_axis(hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), in.axis, eps, ddof, out.device_data_mut()));
+        ++detail::tls_fusion_stats.moments;
+        return out;
+    }
+
     // The ORDER along an axis (np.sort / np.argsort with kind="stable"): sort gives the elements of each line in order, argsort
     // their positions along `axis` as std::int64_t; both have this array's shape and are resident on the device.  Ascending puts
     // the smaller values first and NaNs last (-0 == +0, all NaNs tie); descending = true puts NaNs, then the larger values first.
@@ -1458,6 +1493,35 @@ private:
         hip::check(smhip_sort_axis(descending ? SMHIP_SORT_DESCENDING : SMHIP_SORT_ASCENDING, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(),
                                    in.ndim(), in.axis, want_values ? r.first.device_data_mut() : nullptr, want_where ? r.second.device_data_mut() : nullptr));
         ++detail::tls_fusion_stats.sorts;
+        return r;
+    }
+
+    // {var or stddev, the mean}, of the kept shape (axes == nullptr: over the row-major flattening, shape {1}); the mean has shape {0}
+    // when it is not wanted.
+    std::pair<SMArray, SMArray> moments_of(int kind, const std::initializer_list<int> *axes, std::int64_t ddof, bool keepdims, bool want_mean) const {
+        static_assert(std::is_floating_point_v<T>, "var / stddev / var_mean: float and double only (astype first)");
+        std::uint32_t mask = axes ? 0u : 1u;
+        if (axes) {
+            for (int ax : *axes) {
+                const int a = detail::normal_axis<std::runtime_error>(ax, _shape.size());
+                if (mask >> a & 1u) throw std::runtime_error("simpleMath/MI355X: axis " + std::to_string(ax) + " repeated");
+                mask |= 1u << a;
+            }
+            if (!mask) throw std::runtime_error("simpleMath/MI355X: no axis to reduce");
+        }
+        if (ddof < 0) throw std::runtime_error("simpleMath/MI355X: ddof " + std::to_string(ddof) + " is negative");
+        std::vector<std::size_t> shape = axes ? kept_shape(mask, keepdims) : std::vector<std::size_t>{1};
+        std::int64_t n = 1, results = 1;
+        for (std::size_t d = 0; d < _shape.size(); ++d)
+            if (!axes || (mask >> d & 1u)) n *= static_cast<std::int64_t>(_shape[d]);
+        for (std::size_t e : shape) results *= static_cast<std::int64_t>(e);
+        if (results && n - ddof <= 0) throw std::runtime_error("simpleMath/MI355X: N - ddof = " + std::to_string(n) + " - " + std::to_string(ddof) + " is not positive");
+        hip::DeviceGuard on(device());
+        const AbiView in = axes ? along_axis(0) : flat();  // a pending chain that produces this operand runs here
+        std::pair<SMArray, SMArray> r{device_empty(std::vector<std::size_t>(shape)), device_empty(want_mean ? std::vector<std::size_t>(shape) : std::vector<std::size_t>{0})};
+        hip::check(smhip_moments_axes(kind, hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), mask, ddof, r.first.device_data_mut(),
+                                      want_mean ? r.second.device_data_mut() : nullptr));
+        ++detail::tls_fusion_stats.moments;
         return r;
     }
 

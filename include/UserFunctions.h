@@ -295,6 +295,30 @@ SMArray<T> logsumexp(const SMArray<T> &arr, int axis, bool keepdims = false) { r
 template <typename T>
 SMArray<T> logsumexp(const SMArray<T> &arr) { return arr.logsumexp(); }
 
+// var, stddev and var_mean along axes and standardize along one (float and double): the second moment centred in fp64, one library
+// call each instead of the mean / subtract / square / mean recipe.  The forms without an axis run over the row-major flattening, shape
+// {1}.  Semantics as SMArray::var (SMArray.h) and smhip_moments_axes / smhip_standardize_axis.
+template <typename T>
+SMArray<T> var(const SMArray<T> &arr, int axis, std::int64_t ddof = 0, bool keepdims = false) { return arr.var(axis, ddof, keepdims); }
+template <typename T>
+SMArray<T> var(const SMArray<T> &arr, std::initializer_list<int> axes, std::int64_t ddof = 0, bool keepdims = false) { return arr.var(axes, ddof, keepdims); }
+template <typename T>
+SMArray<T> var(const SMArray<T> &arr) { return arr.var(); }
+template <typename T>
+SMArray<T> stddev(const SMArray<T> &arr, int axis, std::int64_t ddof = 0, bool keepdims = false) { return arr.stddev(axis, ddof, keepdims); }
+template <typename T>
+SMArray<T> stddev(const SMArray<T> &arr, std::initializer_list<int> axes, std::int64_t ddof = 0, bool keepdims = false) { return arr.stddev(axes, ddof, keepdims); }
+template <typename T>
+SMArray<T> stddev(const SMArray<T> &arr) { return arr.stddev(); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<T>> var_mean(const SMArray<T> &arr, int axis, std::int64_t ddof = 0, bool keepdims = false) { return arr.var_mean(axis, ddof, keepdims); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<T>> var_mean(const SMArray<T> &arr, std::initializer_list<int> axes, std::int64_t ddof = 0, bool keepdims = false) { return arr.var_mean(axes, ddof, keepdims); }
+template <typename T>
+std::pair<SMArray<T>, SMArray<T>> var_mean(const SMArray<T> &arr) { return arr.var_mean(); }
+template <typename T>
+SMArray<T> standardize(const SMArray<T> &arr, int axis = -1, double eps = 0.0, std::int64_t ddof = 0) { return arr.standardize(axis, eps, ddof); }
+
 // Picking by position along an axis (np.take_along_axis / np.take): result[..., j, ...] = arr[..., idx[..., j, ...], ...].
 // take_along_axis: `idx` has arr's rank, its other axes equal to arr's or broadcastable; without an axis both are flattened.
 // take: `idx` is 1-D, the result is arr's shape with `axis` replaced by idx.size(); take_flat indexes the row-major flattening.

@@ -602,6 +602,71 @@ int smhip_softmax_axis(int kind, int dtype, const void *a, const int64_t *shape,
 int smhip_softmax_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
                        int *route, int *launches, int64_t *ori3, int64_t *info3);
 
+/* ------------------------------------------------ var / std / standardize */
+/* Centred second moments over chosen axes, f32 and f64 (i32 / i64: SMHIP_ERR_UNSUPPORTED, like MEAN; astype first).  For the N
+ * elements x_k reduced into one output and ddof >= 0:
+ *   mean  = the fp64 sum in a fixed order, divided by N -- what SMHIP_REDUCE_MEAN forms before it rounds;
+ *   d_k   = (double)x_k - mean, in fp64 from the UNROUNDED mean;
+ *   M2    = sum(d_k^2) - (sum d_k)^2 / N, both sums in fp64 in a fixed order (numpy's two-pass definition plus the Chan-Golub-LeVeque
+ *           correction: in exact arithmetic the expression is the true M2 whatever value `mean` has, so the mean's own rounding
+ *           error reaches M2 only at second order);
+ *   VAR   = M2 / (N - ddof), rounded once;   STD = the IEEE fp64 square root of that quotient, rounded once;
+ *   the optional mean output = the fp64 mean rounded once: bit for bit what smhip_reduce_axes(MEAN) writes for the same call.
+ * A line that holds a NaN or an infinity gives NaN (inf - inf); a result above T's range rounds to +inf.  A constant f32 line gives
+ * exactly +0 for N < 2^29 (the fp64 sum of equal floats is exact, so every d_k is +0); the same holds for f64 whenever N * c is exact
+ * in fp64.  The bits depend on kind, dtype, ddof, shape and the layout after merging axes only: not on the run, the stream or the
+ * grid (no float atomics).
+ * Error bounds, derived and not measured; u = 2^-53, u_T = 2^-24 (f32) or 2^-53 (f64), tiny = T's smallest subnormal, exact = the
+ * true value for the given inputs:
+ *   VAR           (u_T + (N + 8) u) exact + tiny
+ *   STD           (u_T + (N/2 + 8) u) exact + tiny
+ *   mean output   MEAN's contract
+ * (d_k carries u, so d_k^2 2u; each term enters sum d^2 by ONE fused multiply-add, and a sum of N terms of one sign costs at most
+ * (N - 1) u in any order; the subtraction of the correction, the division and, for STD, the square root cost u each and the last
+ * rounding u_T: u_T + (N + 4) u, which 8 covers, and the square root halves the relative error it is handed.  The correction term
+ * itself is (sum d)^2 / N = N (mean's error)^2, second order, and its own rounding error is smaller again: the bounds hold to first
+ * order in u and contain neither the mean nor mean / sigma.  They lose their meaning only where sigma < N u |mean|, that is where
+ * the fp64 sum no longer resolves the spread.  For f32 the bound is at most 1.0001 u_T exact + tiny up to N = 5 * 10^4 and
+ * 1.002 u_T exact + tiny at N = 2^20.) */
+typedef enum smhip_moment_kind { SMHIP_MOMENT_VAR = 0, SMHIP_MOMENT_STD = 1 } smhip_moment_kind;
+/* `a` is any view (strides in ELEMENTS, >= 0, 0 broadcasts; rank 1 .. SMHIP_MAX_NDIM); axes_mask as smhip_reduce_axes takes it.  `out`
+ * and the optional mean output are dense row-major over the kept axes in their order, as smhip_reduce_axes writes (1 element when
+ * every axis is reduced); neither may overlap the operand or the other.  Checked before any device is touched: kind, dtype, ndim, the
+ * mask, negative extents or strides, null shape / strides, ddof < 0, an empty reduced extent with something to write, N - ddof <= 0
+ * with something to write (all SMHIP_ERR_INVALID; an integer dtype SMHIP_ERR_UNSUPPORTED), a null buffer with something to write, an
+ * overlap.  Asynchronous, stream-ordered; recorded tiny operators are flushed first. */
+int smhip_moments_axes(int kind, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int64_t ddof,
+                       void *out, void *out_mean_or_null);
+/* Host only, no device touched: the route smhip_moments_axes would take.  *route = a kernel id (SMHIP_MOMENTS_ROUTE_*) ORed with the
+ * flags below; *launches = the kernel launches of the whole call; ori3 = {O, R, I} of the walk after merging; info3 = {L, reads,
+ * levels}: L the longest line held in registers for this dtype (1024 f32, 512 f64: the longest whose register order is the order of
+ * smhip_reduce_axes' sum, which the mean output must reproduce), reads how often the route reads the operand (1 exactly when the line
+ * is held, 2 otherwise; standardize 3: the sums, the centred sums, the store), levels 1 held, 2 otherwise.  Any output may be NULL. */
+#define SMHIP_MOMENTS_ROUTE_NONE 0     /* nothing to write */
+#define SMHIP_MOMENTS_ROUTE_ROW 1      /* I = 1, sr = 1.  R <= L: held, ONE launch -- a segment of 4 / 16 / 64 lanes or a wave per line.
+                                          Longer: smhip_reduce_axes' walk leaves the fp64 sums in a pooled buffer, a second walk (a wave
+                                          per row and chunk) folds (sum d, sum d^2) against sum / N, a finishing launch folds a line's
+                                          chunks in index order and writes */
+#define SMHIP_MOMENTS_ROUTE_COLUMN 2   /* I > 1, si = 1: the same three steps, the second walk a lane per 16 bytes of columns */
+#define SMHIP_MOMENTS_ROUTE_CHANNEL 3  /* smhip_reduce_axes sums it as CHANNEL; the second walk is COLUMN's */
+#define SMHIP_MOMENTS_ROUTE_UNIT 4     /* N = 1: the kept elements copied, then x - x in place (+0, or NaN) */
+#define SMHIP_MOMENTS_SPLIT 0x100      /* the second walk cuts R into more than one chunk (the shape decides) */
+#define SMHIP_MOMENTS_COPY 0x200       /* the operand is copied dense first (no unit stride, a stepped or stride-0 axis), and / or copied
+                                          with the reduced axes innermost (several reduced groups that do not merge; walked as ROW) */
+int smhip_moments_plan(int kind, int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int64_t ddof,
+                       int *route, int *launches, int64_t *ori3, int64_t *info3);
+/* standardize along ONE axis, a result of the operand's shape: y_k = d_k / sqrt(M2 / (N - ddof) + eps), everything in fp64, y_k rounded
+ * once.  A zero denominator (a constant line with eps = 0) gives what the division gives: NaN for 0 / 0.  Bound:
+ *   (u_T + (N + 10) u) |y| + (N + 2) u max_k |x_k| / sqrt(var + eps) + tiny
+ * (the absolute term is the input's own conditioning -- a perturbation of u |x| moves y by that much -- and covers the mean's error).
+ * `out` is dense row-major over `shape`; out == a is allowed when `a` is dense (in place), any other overlap is SMHIP_ERR_INVALID, as
+ * are an axis outside [0, ndim) (not counted from the end), a negative, NaN or infinite eps, ddof < 0 and N - ddof <= 0 with something
+ * to write.  The rest as smhip_moments_axes. */
+int smhip_standardize_axis(int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, double eps, int64_t ddof,
+                           void *out);
+int smhip_standardize_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, double eps, int64_t ddof,
+                           int *route, int *launches, int64_t *ori3, int64_t *info3);
+
 /* ------------------------------------------------ take / take_along_axis */
 /* Picking by position along ONE axis, np.take_along_axis:  out[..., j, ...] = a[..., idx[..., j, ...], ...].  np.take(a, ids,
  * axis) is the same call with the 1-D index array broadcast (stride 0) over every axis but `axis`.  The contract:

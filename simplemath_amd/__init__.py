@@ -61,6 +61,11 @@ SOFTMAX, LOG_SOFTMAX, LOGSUMEXP = range(3)
 SOFTMAX_KINDS = {"softmax": SOFTMAX, "log_softmax": LOG_SOFTMAX, "logsumexp": LOGSUMEXP}
 SOFTMAX_ROUTE_NONE, SOFTMAX_ROUTE_ROW, SOFTMAX_ROUTE_COLUMN, SOFTMAX_ROUTE_FILL = range(4)
 SOFTMAX_SPLIT, SOFTMAX_COPY = 0x100, 0x200
+# smhip_moment_kind, and the route word of smhip_moments_plan / smhip_standardize_plan: a kernel id in the low byte, flags above it
+MOMENT_VAR, MOMENT_STD = range(2)
+MOMENT_KINDS = {"var": MOMENT_VAR, "std": MOMENT_STD}
+MOMENTS_ROUTE_NONE, MOMENTS_ROUTE_ROW, MOMENTS_ROUTE_COLUMN, MOMENTS_ROUTE_CHANNEL, MOMENTS_ROUTE_UNIT = range(5)
+MOMENTS_SPLIT, MOMENTS_COPY = 0x100, 0x200
 INDEX_CHECKED, INDEX_CLIP, INDEX_WRAP = range(3)  # smhip_index_mode
 INDEX_MODES = {"checked": INDEX_CHECKED, "raise": INDEX_CHECKED, "clip": INDEX_CLIP, "wrap": INDEX_WRAP}
 # smhip_take_plan's route word: a kernel id in the low byte, the flag above it
@@ -954,6 +959,129 @@ class Smhip:
         route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
         self._ck(self.c.smhip_softmax_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)),
                                            C.byref(route), C.byref(launches), ori, info))
+        return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
+
+    def var(self, a: DeviceArray, axis=None, ddof=0, keepdims=False, out: DeviceArray | None = None):
+        """np.var(a, axis, ddof=ddof) of `a` (any view, float32 or float64) over `axis` (int, tuple, or None for all): the centred second
+        moment in fp64, rounded once -> a new dense DeviceArray, or into `out`, a dense array of a's dtype with as many elements as the
+        result.  Reducing every axis without keepdims gives shape (1,).  TypeError for an integer dtype; ValueError for a bad or repeated
+        axis, ddof < 0, N - ddof <= 0 or a wrong out."""
+        return self._moments(MOMENT_VAR, "var", a, axis, ddof, keepdims, out, False)
+
+    def std(self, a: DeviceArray, axis=None, ddof=0, keepdims=False, out: DeviceArray | None = None):
+        """np.std(a, axis, ddof=ddof): the fp64 square root of var()'s fp64 quotient, rounded once; arguments as var()."""
+        return self._moments(MOMENT_STD, "std", a, axis, ddof, keepdims, out, False)
+
+    def var_mean(self, a: DeviceArray, axis=None, ddof=0, keepdims=False, out: DeviceArray | None = None):
+        """(var, mean) from one call; the mean's bytes are reduce("mean", ...)'s.  `out` receives the variance."""
+        return self._moments(MOMENT_VAR, "var_mean", a, axis, ddof, keepdims, out, True)
+
+    def _moments(self, kind, name, a, axis, ddof, keepdims, out, with_mean):
+        if a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError(f"{name}: dtype {a.dtype} (float32 and float64 only)")
+        axes = self._axes(a.ndim, axis)
+        ddof = int(ddof)
+        if ddof < 0:
+            raise ValueError(f"{name}: ddof {ddof} is negative")
+        n = int(np.prod([a.shape[d] for d in axes], dtype=np.int64))
+        if keepdims:
+            shape = tuple(1 if d in axes else m for d, m in enumerate(a.shape))
+        else:
+            shape = tuple(m for d, m in enumerate(a.shape) if d not in axes) or (1,)
+        count = int(np.prod(shape, dtype=np.int64))
+        if count and n - ddof <= 0:
+            raise ValueError(f"{name}: N - ddof = {n} - {ddof} is not positive")
+        if out is None:
+            out = self.empty(shape, a.dtype)
+        elif out.dtype != a.dtype or out.size != count or not out.is_dense():
+            raise ValueError(f"{name}: out must be a dense {a.dtype} array of {count} elements (shape {shape}); "
+                             f"got {out.dtype} {out.shape} dense={out.is_dense()}")
+        mean = self.empty(shape, a.dtype) if with_mean else None
+        try:
+            self._ck(self.c.smhip_moments_axes(C.c_int(kind), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(a.shape), _i64(a.strides), C.c_int(a.ndim),
+                                               C.c_uint32(sum(1 << d for d in axes)), C.c_int64(ddof), C.c_void_p(out.ptr),
+                                               C.c_void_p(mean.ptr if with_mean else 0)))
+        except SmhipError as e:
+            if e.code == ERR_INVALID:
+                raise ValueError(str(e)) from None
+            raise
+        return (out, mean) if with_mean else out
+
+    def standardize(self, a: DeviceArray, axis=-1, eps=0.0, ddof=0, out: DeviceArray | None = None):
+        """(a - mean) / sqrt(var + eps) along `axis`, statistics and quotient in fp64, rounded once -> a new dense DeviceArray of a's
+        shape, or into `out`, a dense array of a's shape and dtype; `out` may be `a` itself when `a` is dense (in place).  axis=None takes
+        the row-major flattening and gives shape (a.size,).  TypeError for an integer dtype; ValueError for a bad axis, a negative, NaN
+        or infinite eps, ddof < 0, N - ddof <= 0 or a wrong out."""
+        name = "standardize"
+        if a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError(f"{name}: dtype {a.dtype} (float32 and float64 only)")
+        eps, ddof = float(eps), int(ddof)
+        if not (eps >= 0.0) or eps == float("inf"):
+            raise ValueError(f"{name}: eps {eps} is negative, NaN or infinite")
+        if ddof < 0:
+            raise ValueError(f"{name}: ddof {ddof} is negative")
+        if axis is None:
+            if not a.is_dense():  # the row-major order of a view: its dense copy
+                if out is a:
+                    raise ValueError(f"{name}: out=a (in place) needs a dense array")
+                dense = self.empty(a.shape, a.dtype)
+                self.assign(dense, a)
+                a = dense
+            shape, strides, axis = (a.size,), (1,), 0
+        else:
+            (axis,) = self._axes(a.ndim, int(axis))
+            shape, strides = tuple(a.shape), tuple(a.strides)
+        if int(np.prod(shape, dtype=np.int64)) and shape[axis] - ddof <= 0:
+            raise ValueError(f"{name}: N - ddof = {shape[axis]} - {ddof} is not positive")
+        if out is None:
+            out = self.empty(shape, a.dtype)
+        elif out is a:
+            if not a.is_dense():
+                raise ValueError(f"{name}: out=a (in place) needs a dense array")
+        elif out.dtype != a.dtype or tuple(out.shape) != tuple(shape) or not out.is_dense():
+            raise ValueError(f"{name}: out must be a dense {a.dtype} array of shape {tuple(shape)}; "
+                             f"got {out.dtype} {tuple(out.shape)} dense={out.is_dense()}")
+        try:
+            self._ck(self.c.smhip_standardize_axis(C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(axis),
+                                                   C.c_double(eps), C.c_int64(ddof), C.c_void_p(out.ptr)))
+        except SmhipError as e:
+            if e.code == ERR_INVALID:
+                raise ValueError(str(e)) from None
+            raise
+        return out
+
+    def moments_raw(self, kind, dtype, a_ptr, shape, strides, mask, ddof=0, out_ptr=0, mean_ptr=0, ndim=None):
+        """smhip_moments_axes with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        return self.c.smhip_moments_axes(C.c_int(kind), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                         _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_uint32(mask), C.c_int64(ddof),
+                                         C.c_void_p(out_ptr), C.c_void_p(mean_ptr))
+
+    def standardize_raw(self, dtype, a_ptr, shape, strides, axis, eps=0.0, ddof=0, out_ptr=0, ndim=None):
+        """smhip_standardize_axis with every argument as given (argument-validation tests); ndim defaults to len(shape)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        return self.c.smhip_standardize_axis(C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                             _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_int(axis), C.c_double(eps),
+                                             C.c_int64(ddof), C.c_void_p(out_ptr))
+
+    def moments_plan(self, kind, dtype, shape, strides, axis, ddof=0):
+        """smhip_moments_plan (host only): (route word, launches, (O, R, I), (L, reads, levels)) for a call on shape / strides (elements)."""
+        kind = MOMENT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        axes = self._axes(len(shape), axis)
+        route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        self._ck(self.c.smhip_moments_plan(C.c_int(kind), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)),
+                                           C.c_uint32(sum(1 << d for d in axes)), C.c_int64(int(ddof)), C.byref(route), C.byref(launches), ori, info))
+        return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
+
+    def standardize_plan(self, dtype, shape, strides, axis, eps=0.0, ddof=0):
+        """smhip_standardize_plan (host only): the same four for standardize along `axis`."""
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        self._ck(self.c.smhip_standardize_plan(C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)), C.c_double(float(eps)),
+                                               C.c_int64(int(ddof)), C.byref(route), C.byref(launches), ori, info))
         return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
 
     def take_along_axis(self, a: DeviceArray, idx: DeviceArray, axis, mode="checked", out: DeviceArray | None = None):

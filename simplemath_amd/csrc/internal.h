@@ -233,6 +233,10 @@ void sort_axis_plan(int dtype, const int64_t *shape, const int64_t *strides, int
                     int64_t *chunk);
 int launch_sort_axis(int order, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis, void *values_out,
                      int64_t *index_out, hipStream_t s);
+// reduce_axis.hip: the route smhip_reduce_axes takes for a call, and the call's SUM left in fp64 (dense over the kept axes, as the
+// reduction writes it) -- f32 and f64, some reduced extent > 1; moments_axis.hip centres on it
+void reduce_sum_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int *route, int *launches, int64_t *ori3);
+int launch_reduce_sum64(int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, double *out, hipStream_t s);
 // select.hip: the exclusive prefix of per-tile counts in ONE workgroup (offsets, when given) and their sum (*total, when given), exact in
 // int64; unique.hip's compaction runs the same launch between its count and its emit.
 int launch_tile_scan(const int32_t *counts, int64_t tiles, int64_t *offsets, int64_t *total, hipStream_t s);

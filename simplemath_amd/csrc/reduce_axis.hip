@@ -461,8 +461,9 @@ int run_pass(const Pass &p, const TI *in, TO *out, OutMap om, double divisor, hi
 }
 
 // T: element type; S: what partial and intermediate results are kept in (fp64 for float sums, T otherwise).
-template <typename T, int K>
-int run_plan(const Plan &pl, int dtype, const T *a, const int64_t *shape, const int64_t *strides, int ndim, T *out, double divisor, hipStream_t s) {
+// TO: what the call writes -- T, or double for the unrounded fp64 sum (launch_reduce_sum64).
+template <typename T, typename TO, int K>
+int run_plan(const Plan &pl, int dtype, const T *a, const int64_t *shape, const int64_t *strides, int ndim, TO *out, double divisor, hipStream_t s) {
     typedef typename std::conditional<K == kSum && std::is_floating_point<T>::value, double, T>::type S;
     Pooled copy, tmp[2];
     const void *dense = a;
@@ -472,14 +473,14 @@ int run_plan(const Plan &pl, int dtype, const T *a, const int64_t *shape, const 
     const int np = pl.npasses;
     if (np == 1) {
         const Pass &p = pl.pass[0];
-        return run_pass<T, T, S, K>(p, in, out, OutMap{p.oso, p.osi, 0}, divisor, s);
+        return run_pass<T, TO, S, K>(p, in, out, OutMap{p.oso, p.osi, 0}, divisor, s);
     }
     // several reduced groups: T -> S, S -> S ..., S -> T (the mean's division at the very end)
     const S *prev = nullptr;
     for (int k = 0; k < np; ++k) {
         const Pass &p = pl.pass[k];
         const OutMap om{p.oso, p.osi, 0};
-        if (k == np - 1) return run_pass<S, T, S, K>(p, prev, out, om, divisor, s);
+        if (k == np - 1) return run_pass<S, TO, S, K>(p, prev, out, om, divisor, s);
         void *buf;  // the pass two back, whose result this owner hands back first, has been queued before
         if (int rc = tmp[k & 1].take((size_t)(p.O * p.I) * sizeof(S), &buf)) return rc;
         S *dst = static_cast<S *>(buf);
@@ -495,10 +496,10 @@ int run_kind(int kind, const Plan &pl, int dtype, const void *a, const int64_t *
     const T *pa = static_cast<const T *>(a);
     T *po = static_cast<T *>(out);
     switch (kind) {
-        case SMHIP_REDUCE_SUM: return run_plan<T, kSum>(pl, dtype, pa, shape, strides, ndim, po, 0.0, s);
-        case SMHIP_REDUCE_MEAN: return run_plan<T, kSum>(pl, dtype, pa, shape, strides, ndim, po, (double)pl.total_r, s);
-        case SMHIP_REDUCE_MAX: return run_plan<T, kMax>(pl, dtype, pa, shape, strides, ndim, po, 0.0, s);
-        case SMHIP_REDUCE_MIN: return run_plan<T, kMin>(pl, dtype, pa, shape, strides, ndim, po, 0.0, s);
+        case SMHIP_REDUCE_SUM: return run_plan<T, T, kSum>(pl, dtype, pa, shape, strides, ndim, po, 0.0, s);
+        case SMHIP_REDUCE_MEAN: return run_plan<T, T, kSum>(pl, dtype, pa, shape, strides, ndim, po, (double)pl.total_r, s);
+        case SMHIP_REDUCE_MAX: return run_plan<T, T, kMax>(pl, dtype, pa, shape, strides, ndim, po, 0.0, s);
+        case SMHIP_REDUCE_MIN: return run_plan<T, T, kMin>(pl, dtype, pa, shape, strides, ndim, po, 0.0, s);
     }
     return fail(SMHIP_ERR_INVALID, "reduce_axes: bad kind %d", kind);
 }
@@ -539,6 +540,19 @@ int launch_reduce_axes(int kind, int dtype, const void *a, const int64_t *shape,
 }
 
 }  // namespace
+
+// What moments_axis.hip takes from here: the route of a call, and the call's sums kept in fp64 -- what MEAN divides before it rounds.
+void reduce_sum_plan(int dtype, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, int *route, int *launches, int64_t *ori3) {
+    reduce_axes_plan(dtype, shape, strides, ndim, axes_mask, route, launches, ori3);
+}
+int launch_reduce_sum64(int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, uint32_t axes_mask, double *out, hipStream_t s) {
+    Plan pl;
+    make_plan(dtype, shape, strides, ndim, axes_mask, &pl);
+    if (pl.npasses == 0 || (dtype != SMHIP_F32 && dtype != SMHIP_F64)) return fail(SMHIP_ERR_INVALID, "reduce_sum64: no walk for this call");
+    if (dtype == SMHIP_F64) return run_plan<double, double, kSum>(pl, dtype, static_cast<const double *>(a), shape, strides, ndim, out, 0.0, s);
+    return run_plan<float, double, kSum>(pl, dtype, static_cast<const float *>(a), shape, strides, ndim, out, 0.0, s);
+}
+
 }  // namespace smhip
 
 using namespace smhip;
