@@ -74,6 +74,16 @@ enum class index_mode {
     wrap = SMHIP_INDEX_WRAP,        // the non-negative remainder mod R (np.take(mode="wrap")): fully asynchronous
 };
 
+// How sm::quantile reads a probability whose position h = (R - 1) q falls between two elements of the ordered line (smhip.h:
+// smhip_quantile_method): numpy's method names.
+enum class quantile_method {
+    linear = SMHIP_QUANTILE_LINEAR,      // interpolate between s[floor(h)] and the next, in fp64, rounded once
+    lower = SMHIP_QUANTILE_LOWER,        // s[floor(h)]
+    higher = SMHIP_QUANTILE_HIGHER,      // s[ceil(h)]
+    nearest = SMHIP_QUANTILE_NEAREST,    // s[rint(h)], ties to even
+    midpoint = SMHIP_QUANTILE_MIDPOINT,  // halfway between the two where h is not an integer
+};
+
 // Which of equal edges sm::searchsorted names (smhip.h: smhip_side): np.searchsorted's side.
 enum class side {
     left = SMHIP_SIDE_LEFT,    // the first i with !(edges[i] before x): a value equal to an edge stands AT the edge's first copy
@@ -121,6 +131,7 @@ struct FusionStats {
     unsigned long long selects = 0;             // smhip_where / smhip_select_count / smhip_select calls
     unsigned long long uniques = 0;             // smhip_runs_count / smhip_runs calls: unique_* / unique_consecutive / run_lengths (a count, then the runs)
     unsigned long long topks = 0;               // smhip_topk_axis calls: topk / topk_flat
+    unsigned long long quantiles = 0;           // smhip_quantile_axis calls: quantile / percentile / median
     unsigned long long softmaxes = 0;           // smhip_softmax_axis calls: softmax / log_softmax / logsumexp
     unsigned long long moments = 0;             // smhip_moments_axes / smhip_standardize_axis calls: var / stddev / var_mean / standardize
 };
@@ -912,6 +923,30 @@ public:
     std::pair<SMArray, SMArray<std::int64_t>> topk(std::size_t k, int axis = -1, bool largest = true) const { return topk_of(k, axis, largest); }
     std::pair<SMArray, SMArray<std::int64_t>> topk_flat(std::size_t k, bool largest = true) const { return topk_of(k, std::nullopt, largest); }
 
+    // ORDER STATISTICS along an axis without sorting the line (np.quantile / np.percentile / np.median): the element of the ordered line
+    // at position (R - 1) q, interpolated in fp64 and rounded once where that falls between two (quantile_method; smhip.h, "quantile",
+    // has the rules); float and double only (a static_assert; astype first).  A line that holds a NaN gives NaN, every zero is read as
+    // +0.  A single q gives the kept shape (keepdims keeps the axis as an extent of 1); a list of Q gives a leading axis of Q in front
+    // of it, from ONE read of the operand; the forms without an axis run over the row-major flattening and give shape {1}, or {Q}.
+    // `axis` counts from the end when negative.  The operand may be a view or a pending chain (evaluated first); each is ONE
+    // smhip_quantile_axis call (counted in sm::fusion_stats().quantiles) whose result stays on the device and feeds the next chain:
+    // `(x - x.median(-1, true)) / (x.quantile(0.75, -1, m, true) - x.quantile(0.25, -1, m, true))`.  An axis out of range, a q outside
+    // [0, 1] or NaN, an empty list and an empty axis with a result that is not empty throw std::invalid_argument.
+    SMArray quantile(double q, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) const { return quantile_of(&q, 1, false, axis, method, keepdims, 1.0, "quantile: "); }
+    SMArray quantile(std::initializer_list<double> q, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) const { return quantile_of(q.begin(), q.size(), true, axis, method, keepdims, 1.0, "quantile: "); }
+    SMArray quantile(const std::vector<double> &q, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) const { return quantile_of(q.data(), q.size(), true, axis, method, keepdims, 1.0, "quantile: "); }
+    SMArray quantile(double q, quantile_method method = quantile_method::linear) const { return quantile_of(&q, 1, false, std::nullopt, method, false, 1.0, "quantile: "); }
+    SMArray quantile(std::initializer_list<double> q, quantile_method method = quantile_method::linear) const { return quantile_of(q.begin(), q.size(), true, std::nullopt, method, false, 1.0, "quantile: "); }
+    SMArray quantile(const std::vector<double> &q, quantile_method method = quantile_method::linear) const { return quantile_of(q.data(), q.size(), true, std::nullopt, method, false, 1.0, "quantile: "); }
+    SMArray percentile(double p, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) const { return quantile_of(&p, 1, false, axis, method, keepdims, 100.0, "percentile: "); }
+    SMArray percentile(std::initializer_list<double> p, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) const { return quantile_of(p.begin(), p.size(), true, axis, method, keepdims, 100.0, "percentile: "); }
+    SMArray percentile(const std::vector<double> &p, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) const { return quantile_of(p.data(), p.size(), true, axis, method, keepdims, 100.0, "percentile: "); }
+    SMArray percentile(const std::vector<double> &p, quantile_method method = quantile_method::linear) const { return quantile_of(p.data(), p.size(), true, std::nullopt, method, false, 100.0, "percentile: "); }
+    SMArray percentile(double p, quantile_method method = quantile_method::linear) const { return quantile_of(&p, 1, false, std::nullopt, method, false, 100.0, "percentile: "); }
+    SMArray percentile(std::initializer_list<double> p, quantile_method method = quantile_method::linear) const { return quantile_of(p.begin(), p.size(), true, std::nullopt, method, false, 100.0, "percentile: "); }
+    SMArray median(int axis, bool keepdims = false) const { const double q = 0.5; return quantile_of(&q, 1, false, axis, quantile_method::linear, keepdims, 1.0, "median: "); }
+    SMArray median() const { const double q = 0.5; return quantile_of(&q, 1, false, std::nullopt, quantile_method::linear, false, 1.0, "median: "); }
+
     // PICKING BY POSITION along an axis (np.take_along_axis / np.take): the consumer of what argmax, argsort and sort_with_index
     // produce.  take_along_axis: `idx` is an SMArray<std::int64_t> of this array's rank whose other axes equal this array's
     // or broadcast against them; result[..., j, ...] = (*this)[..., idx[..., j, ...], ...], of the broadcast shape with idx's
@@ -1552,6 +1587,36 @@ private:
                                    in.ndim(), in.axis, static_cast<std::int64_t>(k), r.first.device_data_mut(), r.second.device_data_mut()));
         ++detail::tls_fusion_stats.topks;
         return r;
+    }
+
+    // The quantiles of `n` probabilities (each divided by `scale`: 100 for percentiles), of the kept shape (without an axis: {1}) with a
+    // leading axis of n when they came as a list.
+    SMArray quantile_of(const double *q, std::size_t n, bool list, std::optional<int> axis, quantile_method method, bool keepdims, double scale, const char *who) const {
+        static_assert(std::is_floating_point_v<T>, "quantile / percentile / median: float and double only (astype first)");
+        if (axis) axis = detail::normal_axis<std::invalid_argument>(*axis, _shape.size(), who);
+        if (n == 0) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + who + "no probability given");
+        std::vector<double> qs(q, q + n);
+        for (double &v : qs) {
+            if (scale != 1.0) v /= scale;
+            if (!(v >= 0.0 && v <= 1.0)) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + who + "a probability outside [0, " + (scale == 1.0 ? "1" : "100") + "] or NaN");
+        }
+        std::vector<std::size_t> shape;
+        if (list) shape.push_back(n);
+        for (std::size_t d = 0; axis && d < _shape.size(); ++d) {
+            if (static_cast<int>(d) != *axis) shape.push_back(_shape[d]);
+            else if (keepdims) shape.push_back(1);
+        }
+        if (shape.empty()) shape.push_back(1);
+        std::size_t results = 1;
+        for (std::size_t e : shape) results *= e;
+        if (results && (axis ? _shape[*axis] : totalSize) == 0) throw std::invalid_argument(std::string("simpleMath/MI355X: ") + who + "an empty axis with a result that is not empty");
+        hip::DeviceGuard on(device());
+        const AbiView in = line(axis);  // a pending chain that produces this operand runs here
+        SMArray out = device_empty(std::move(shape));
+        hip::check(smhip_quantile_axis(static_cast<int>(method), hip::dtype_of<T>::id, in.ptr, in.shape.data(), in.strides.data(), in.ndim(), in.axis, qs.data(),
+                                       static_cast<std::int64_t>(qs.size()), out.device_data_mut()));
+        ++detail::tls_fusion_stats.quantiles;
+        return out;
     }
 
     // Both operands in row-major order as one line each (views are made dense first), shape {idx.size()}.

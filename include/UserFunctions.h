@@ -283,6 +283,38 @@ std::pair<SMArray<T>, SMArray<std::int64_t>> topk(const SMArray<T> &arr, std::si
 template <typename T>
 std::pair<SMArray<T>, SMArray<std::int64_t>> topk_flat(const SMArray<T> &arr, std::size_t k, bool largest = true) { return arr.topk_flat(k, largest); }
 
+// Order statistics along an axis without sorting the line (np.quantile / np.percentile / np.median): a single probability gives the
+// kept shape, a list of Q a leading axis of Q, from one read of the operand; the forms without an axis run over the row-major
+// flattening, shape {1} or {Q}.  Semantics as SMArray::quantile (SMArray.h) and smhip_quantile_axis.
+template <typename T>
+SMArray<T> quantile(const SMArray<T> &arr, double q, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) { return arr.quantile(q, axis, method, keepdims); }
+template <typename T>
+SMArray<T> quantile(const SMArray<T> &arr, std::initializer_list<double> q, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) { return arr.quantile(q, axis, method, keepdims); }
+template <typename T>
+SMArray<T> quantile(const SMArray<T> &arr, const std::vector<double> &q, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) { return arr.quantile(q, axis, method, keepdims); }
+template <typename T>
+SMArray<T> quantile(const SMArray<T> &arr, double q, quantile_method method = quantile_method::linear) { return arr.quantile(q, method); }
+template <typename T>
+SMArray<T> quantile(const SMArray<T> &arr, std::initializer_list<double> q, quantile_method method = quantile_method::linear) { return arr.quantile(q, method); }
+template <typename T>
+SMArray<T> quantile(const SMArray<T> &arr, const std::vector<double> &q, quantile_method method = quantile_method::linear) { return arr.quantile(q, method); }
+template <typename T>
+SMArray<T> percentile(const SMArray<T> &arr, double p, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) { return arr.percentile(p, axis, method, keepdims); }
+template <typename T>
+SMArray<T> percentile(const SMArray<T> &arr, std::initializer_list<double> p, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) { return arr.percentile(p, axis, method, keepdims); }
+template <typename T>
+SMArray<T> percentile(const SMArray<T> &arr, const std::vector<double> &p, int axis, quantile_method method = quantile_method::linear, bool keepdims = false) { return arr.percentile(p, axis, method, keepdims); }
+template <typename T>
+SMArray<T> percentile(const SMArray<T> &arr, const std::vector<double> &p, quantile_method method = quantile_method::linear) { return arr.percentile(p, method); }
+template <typename T>
+SMArray<T> percentile(const SMArray<T> &arr, double p, quantile_method method = quantile_method::linear) { return arr.percentile(p, method); }
+template <typename T>
+SMArray<T> percentile(const SMArray<T> &arr, std::initializer_list<double> p, quantile_method method = quantile_method::linear) { return arr.percentile(p, method); }
+template <typename T>
+SMArray<T> median(const SMArray<T> &arr, int axis, bool keepdims = false) { return arr.median(axis, keepdims); }
+template <typename T>
+SMArray<T> median(const SMArray<T> &arr) { return arr.median(); }
+
 // softmax, log_softmax and logsumexp along an axis, fused per line (float and double): one library call each instead of the
 // max / exp / sum / divide recipe.  logsumexp without an axis runs over the row-major flattening, shape {1}.  Semantics as
 // SMArray::softmax (SMArray.h) and smhip_softmax_axis.

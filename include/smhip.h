@@ -553,6 +553,68 @@ int smhip_topk_axis(int order, int dtype, const void *a, const int64_t *shape, c
 int smhip_topk_plan(int order, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis, int64_t k,
                     int *route, int *launches, int64_t *ori3, int64_t *info3);
 
+/* ---------------------------------------- quantile / percentile / median */
+/* np.quantile along ONE axis without sorting the line, f32 and f64 (i32 / i64: SMHIP_ERR_UNSUPPORTED, like var; astype first).  For a
+ * line of R elements and a probability q in [0, 1], let s_0 .. s_{R-1} be the line in smhip_sort_axis' ASCENDING order, every zero read
+ * as +0 (the order does not distinguish the zeros, so an element that is a zero is always returned as +0).  On the host, in fp64:
+ *   h = (R - 1) * q (one rounding),  j = floor(h),  g = h - j (exact)
+ *   method      result
+ *   LINEAR      lo = s[j], hi = s[min(j + 1, R - 1)], interpolated as below with g
+ *   LOWER       s[floor(h)]
+ *   HIGHER      s[ceil(h)]
+ *   NEAREST     s[rint(h)], ties to even (numpy's rule)
+ *   MIDPOINT    LINEAR with g = 0.5 when h is not an integer, else s[h]
+ * Interpolation, in fp64 from the exactly converted elements, each step ONE IEEE operation (never a fused multiply-add):
+ *   g == 0      lo; hi is not consulted
+ *   lo == hi    lo.  Two equal infinities therefore give that infinity (np.quantile gives NaN there, np.median does not)
+ *   otherwise   with d = hi - lo:  lo + d * g when g < 0.5, else hi - d * (1 - g) (numpy's _lerp); rounded to T ONCE
+ * An infinite neighbour with 0 < g < 1 gives what the formula gives, d being infinite: -inf and +inf as neighbours give NaN (-inf + inf
+ * or inf - inf); one infinite neighbour gives that infinity where the formula starts from the finite one (hi = +inf with g < 0.5,
+ * lo = -inf with g >= 0.5) and NaN where it starts from the infinite one.  An fp64 d that overflows (f64 only) likewise gives what the
+ * formula gives: an infinity.  A line that holds a NaN gives NaN for every method.  Every NaN result is the canonical quiet NaN (0x7fc00000, 0x7ff8000000000000).  A result that is not an element can
+ * be -0 only where the final rounding to T underflows from a negative fp64 value.
+ * Error: an element is returned exactly.  An interpolated result is the correctly rounded (to T) value of an fp64 expression that
+ * carries three roundings (d, the product, the sum; 1 - g is exact for g >= 0.5), on top of h's one: for f32 that is
+ * |error| <= (2^-24 + 3 * 2^-53) max(|lo|, |hi|) against the exact lo + (hi - lo) g of the g computed above.
+ * MEDIAN is q = 0.5, percentile(p) is quantile(p / 100) with the division done by the caller in fp64.
+ * The bytes are the same on every run, stream and grid, whatever the route: the only atomics are integer counts, and an element is
+ * taken from the line, never rebuilt from its key. */
+typedef enum smhip_quantile_method {
+    SMHIP_QUANTILE_LINEAR = 0, SMHIP_QUANTILE_LOWER = 1, SMHIP_QUANTILE_HIGHER = 2, SMHIP_QUANTILE_NEAREST = 3, SMHIP_QUANTILE_MIDPOINT = 4
+} smhip_quantile_method;
+/* `a` is any view (strides in ELEMENTS, >= 0, 0 broadcasts; rank 1 .. SMHIP_MAX_NDIM); `axis` in [0, ndim), not counted from the end.
+ * `q` is a HOST array of nq doubles; it is read before the call returns.  `out` is dense row-major [nq][the other axes in their order]
+ * (nq elements when ndim == 1) and may not overlap the operand.  Checked before any device is touched and before anything is queued:
+ * method, dtype, ndim (SMHIP_ERR_INVALID), an integer dtype (SMHIP_ERR_UNSUPPORTED), axis, negative extents or strides, null shape /
+ * strides / q, nq < 1, a q[i] outside [0, 1] or NaN (SMHIP_ERR_INVALID), shape[axis] >= 2^31 (SMHIP_ERR_UNSUPPORTED), shape[axis] == 0
+ * while the result is not empty, null a / out with something to write, an overlap (SMHIP_ERR_INVALID).  Another extent of 0 is a no-op,
+ * whatever the pointers.  The operand is read once for all nq probabilities wherever the route holds the line on chip.  Asynchronous,
+ * stream-ordered: it is ordered behind everything queued and everything later behind it; recorded tiny operators are flushed first. */
+int smhip_quantile_axis(int method, int dtype, const void *a, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                        const double *q, int64_t nq, void *out);
+/* Host only, no device touched: the route smhip_quantile_axis would take.  *route = a kernel id (SMHIP_QUANTILE_ROUTE_*) ORed with the
+ * flags below; *launches = the kernel launches of the whole call (SORT: the sort's as smhip_sort_plan counts them, plus the picks);
+ * ori3 = {O, R, I} as smhip_sort_plan reports them; info3 = {L, Qmax, reads}: L the longest line a selection holds in LDS and the most
+ * elements a streamed rank is compacted to, Qmax the most probabilities a selection serves (both the same for every shape), reads how
+ * often the route reads the operand at most (1 held or sorted; STREAM: a pass per key byte and the compaction -- a line stops reading
+ * as soon as every rank's candidates fit L, after 2 to 3 passes on continuous data).  Any output may be NULL. */
+#define SMHIP_QUANTILE_ROUTE_NONE 0      /* a kept extent is 0: nothing to compute */
+#define SMHIP_QUANTILE_ROUTE_COPYONLY 1  /* R = 1: the line's element (a zero as +0), or NaN for a NaN: a dense copy, then the picks,
+                                            Qmax probabilities a launch */
+#define SMHIP_QUANTILE_ROUTE_ROW 2       /* nq <= Qmax: a line (R <= L) is loaded into LDS once and every rank wanted is found by a radix
+                                            select over a monotone key, 8 bits a pass: ONE launch.  With SMHIP_QUANTILE_STREAM (R > L) the
+                                            passes run over the line in memory, counting into a pooled table per line and rank, until a
+                                            rank's candidates are at most L; those are compacted and selected from in LDS */
+#define SMHIP_QUANTILE_ROUTE_SORT 3      /* nq > Qmax; more distinct ranks wanted (lo and hi of every probability) than a selection in LDS
+                                            serves ahead of the sort -- 2 for R <= L / 4, 8 for R <= L, measured; or a STREAM whose
+                                            compaction buffers (lines * ranks * L elements) would exceed 256 MiB: smhip_sort_axis's kernels into a pooled array, then s[j] and s[j + 1] picked and
+                                            interpolated, Qmax probabilities a launch */
+#define SMHIP_QUANTILE_STREAM 0x100      /* R > L on ROUTE_ROW */
+#define SMHIP_QUANTILE_COPY 0x200        /* staging, decided as smhip_sort_plan decides it: the operand copied so that the axis is the
+                                            unit-stride one, and / or the result rows scattered to the dense result (one launch) */
+int smhip_quantile_plan(int method, int dtype, const int64_t *shape, const int64_t *strides, int ndim, int axis,
+                        const double *q, int64_t nq, int *route, int *launches, int64_t *ori3, int64_t *info3);
+
 /* --------------------------------------- softmax / log_softmax / logsumexp */
 /* Along ONE axis, fused per line, f32 and f64.  For a line x_0 .. x_{R-1} with maximum m and d_r = x_r - m:
  *   the line              SOFTMAX            LOG_SOFTMAX        LOGSUMEXP

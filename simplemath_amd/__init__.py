@@ -56,6 +56,11 @@ SORT_MERGE, SORT_COPY = 0x100, 0x200
 TOPK_ROUTE_NONE, TOPK_ROUTE_COPYONLY, TOPK_ROUTE_ROW, TOPK_ROUTE_SORT = range(4)
 TOPK_TILED, TOPK_COPY = 0x100, 0x200
 TOPK_RANKED = 128  # SMHIP_TOPK_RANKED: the longest line that is ranked, whatever k is
+# smhip_quantile_method, and smhip_quantile_plan's route word: a kernel id in the low byte, flags above it
+QUANTILE_LINEAR, QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_NEAREST, QUANTILE_MIDPOINT = range(5)
+QUANTILE_METHODS = {"linear": QUANTILE_LINEAR, "lower": QUANTILE_LOWER, "higher": QUANTILE_HIGHER, "nearest": QUANTILE_NEAREST, "midpoint": QUANTILE_MIDPOINT}
+QUANTILE_ROUTE_NONE, QUANTILE_ROUTE_COPYONLY, QUANTILE_ROUTE_ROW, QUANTILE_ROUTE_SORT = range(4)
+QUANTILE_STREAM, QUANTILE_COPY = 0x100, 0x200
 # smhip_softmax_kind, and smhip_softmax_plan's route word: a kernel id in the low byte, flags above it
 SOFTMAX, LOG_SOFTMAX, LOGSUMEXP = range(3)
 SOFTMAX_KINDS = {"softmax": SOFTMAX, "log_softmax": LOG_SOFTMAX, "logsumexp": LOGSUMEXP}
@@ -896,6 +901,84 @@ class Smhip:
         route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
         self._ck(self.c.smhip_topk_plan(C.c_int(SORT_DESCENDING if largest else SORT_ASCENDING), C.c_int(dtype), _i64(shape), _i64(strides),
                                         C.c_int(len(shape)), C.c_int(int(axis)), C.c_int64(int(k)), C.byref(route), C.byref(launches), ori, info))
+        return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
+
+    def quantile(self, a: DeviceArray, q, axis=-1, method="linear", keepdims=False, out: DeviceArray | None = None):
+        """np.quantile(a, q, axis, method=method) of `a` (any view, float32 or float64) along `axis`, one call -> a new dense DeviceArray
+        over the other axes (keepdims=True: with extent 1 along the axis), with a leading axis of len(q) when q is a sequence; or into
+        `out`, a dense array of a's dtype with as many elements, never the operand.  axis=None runs over the row-major flattening (a
+        scalar q then gives shape (1,)).  method: linear, lower, higher, nearest or midpoint.  A line that holds a NaN gives NaN; every
+        zero is read as +0.  TypeError for an integer dtype (astype first); ValueError for a bad axis, method, q outside [0, 1] or NaN,
+        an empty q, an empty axis with a result that is not empty, or a wrong out."""
+        return self._quantile("quantile", a, q, axis, method, keepdims, out, 1.0)
+
+    def percentile(self, a: DeviceArray, p, axis=-1, method="linear", keepdims=False, out: DeviceArray | None = None):
+        """quantile(a, p / 100, ...): the division is one fp64 operation per entry."""
+        return self._quantile("percentile", a, p, axis, method, keepdims, out, 100.0)
+
+    def median(self, a: DeviceArray, axis=-1, keepdims=False, out: DeviceArray | None = None):
+        """quantile(a, 0.5, axis): the middle element, or the mean of the two middle ones formed as the interpolation forms it."""
+        return self._quantile("median", a, 0.5, axis, "linear", keepdims, out, 1.0)
+
+    def _quantile(self, name, a, q, axis, method, keepdims, out, scale):
+        if a.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError(f"{name}: dtype {a.dtype} (float32 and float64 only: astype first)")
+        if method not in QUANTILE_METHODS:
+            raise ValueError(f"{name}: method {method!r} (one of {', '.join(QUANTILE_METHODS)})")
+        scalar = np.ndim(q) == 0
+        qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+        if qs.ndim != 1 or qs.size == 0:
+            raise ValueError(f"{name}: q must be a number or a non-empty 1-D sequence")
+        qs = qs / scale if scale != 1.0 else qs
+        if not bool(np.all((qs >= 0.0) & (qs <= 1.0))):
+            raise ValueError(f"{name}: q outside [0, {scale:g}] or NaN")
+        if axis is None:
+            if not a.is_dense():  # the row-major order of a view: its dense copy
+                dense = self.empty(a.shape, a.dtype)
+                self.assign(dense, a)
+                a = dense
+            shape, strides, axis = (a.size,), (1,), 0
+            kept = (1,) * a.ndim if keepdims else ()
+        else:
+            (axis,) = self._axes(a.ndim, int(axis))
+            shape, strides = tuple(a.shape), tuple(a.strides)
+            kept = shape[:axis] + ((1,) if keepdims else ()) + shape[axis + 1:]
+        result_shape = (() if scalar else (qs.size,)) + kept or (1,)
+        count = int(np.prod(result_shape, dtype=np.int64))
+        if count and shape[axis] == 0:
+            raise ValueError(f"{name}: an empty axis with a result that is not empty")
+        if out is None:
+            out = self.empty(result_shape, a.dtype)
+        elif out.dtype != a.dtype or out.size != count or not out.is_dense():
+            raise ValueError(f"{name}: out must be a dense {a.dtype} array of {count} elements (shape {result_shape}); "
+                             f"got {out.dtype} {out.shape} dense={out.is_dense()}")
+        try:
+            self._ck(self.c.smhip_quantile_axis(C.c_int(QUANTILE_METHODS[method]), C.c_int(DTYPES[a.dtype]), C.c_void_p(a.ptr), _i64(shape), _i64(strides),
+                                                C.c_int(len(shape)), C.c_int(axis), (C.c_double * qs.size)(*qs.tolist()), C.c_int64(qs.size), C.c_void_p(out.ptr)))
+        except SmhipError as e:
+            if e.code == ERR_INVALID:
+                raise ValueError(str(e)) from None
+            raise
+        return out
+
+    def quantile_raw(self, method, dtype, a_ptr, shape, strides, axis, q, out_ptr=0, ndim=None, nq=None):
+        """smhip_quantile_axis with every argument as given (argument-validation tests); ndim defaults to len(shape), nq to len(q)."""
+        if ndim is None:
+            ndim = len(shape) if shape is not None else 0
+        if nq is None:
+            nq = len(q) if q is not None else 0
+        return self.c.smhip_quantile_axis(C.c_int(method), C.c_int(dtype), C.c_void_p(a_ptr), _i64(shape) if shape is not None else None,
+                                          _i64(strides) if strides is not None else None, C.c_int(ndim), C.c_int(axis),
+                                          (C.c_double * max(len(q), 1))(*q) if q is not None else None, C.c_int64(nq), C.c_void_p(out_ptr))
+
+    def quantile_plan(self, dtype, shape, strides, axis, q, method="linear"):
+        """smhip_quantile_plan (host only): (route word, launches, (O, R, I), (L, Qmax, reads)) for a call on shape / strides (elements)."""
+        dtype = DTYPES[np.dtype(dtype)] if not isinstance(dtype, int) else dtype
+        method = QUANTILE_METHODS[method] if isinstance(method, str) else int(method)
+        qs = [float(x) for x in np.atleast_1d(q)]
+        route, launches, ori, info = C.c_int(0), C.c_int(0), (C.c_int64 * 3)(), (C.c_int64 * 3)()
+        self._ck(self.c.smhip_quantile_plan(C.c_int(method), C.c_int(dtype), _i64(shape), _i64(strides), C.c_int(len(shape)), C.c_int(int(axis)),
+                                            (C.c_double * len(qs))(*qs), C.c_int64(len(qs)), C.byref(route), C.byref(launches), ori, info))
         return route.value, launches.value, tuple(int(x) for x in ori), tuple(int(x) for x in info)
 
     def softmax(self, a: DeviceArray, axis=-1, out: DeviceArray | None = None):
